@@ -9,6 +9,14 @@ synchronize on every rank; value = sum(num_steps) over all chains and ranks / ma
 wall time (useful leapfrogs, inputs resident in HBM).  Timing adapted chains matters: with
 the step size still at its initial value most trees are one divergent leaf.
 
+A plain run does only that and prints the result line.  `--full` adds everything else the
+benchmark measures or checks: the end-of-run exchange, the CPU baseline and full-size parity of
+the headline, and the BASELINE.json secondary configs with their CPU comparators (`--configs`,
+`--no-cpu-baseline` and the CPU budgets select among them).  `--dump-outputs DIR` writes what
+the last timed transition produced (every chain's draw and its collected fields) as
+DIR/<name>.npy; the data and every seed are fixed by the arguments, so two builds can be
+compared output for output.
+
 Launch for N GPUs:  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 from __future__ import annotations
@@ -39,23 +47,32 @@ def parse():
     p.add_argument("--chains", type=int, default=4096, help="total chains over all GPUs")
     p.add_argument("--rows", type=int, default=581012)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: end-of-run exchange, CPU baseline and "
+                        "parity of the headline, the secondary configs (see --configs, --no-cpu-baseline)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the last timed transition's outputs (draws and collected fields of every chain) "
+                        "as DIR/<name>.npy, float32")
     p.add_argument("--design", default="iid", choices=["iid", "structured"],
                    help="synthetic covtype design: iid N(0,1) columns (default) or the real data's structure "
                         "(one-hot groups collinear with the intercept: depth-saturated trees, datasets.covtype_structured)")
     p.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline budget (headline)")
     p.add_argument("--config-cpu-seconds", type=float, default=8.0, help="CPU baseline budget per config")
     p.add_argument("--cpu-chains", type=int, default=64, help="chains of the CPU baseline sample")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baselines and parity")
     p.add_argument("--sync-chains", action="store_true", help="reference lockstep schedule")
     p.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_r06.json"))
     p.add_argument("--configs", default="c2,c3,c4",
-                   help="BASELINE.json secondary configs measured after the headline (comma list of c2 funnel-10k "
+                   help="(with --full) BASELINE.json secondary configs measured after the headline (comma list of c2 funnel-10k "
                         "dense, c3 BNN dense, c4 stochastic volatility; 'none' skips); c2/c3 are one-GPU configs "
                         "and run at --gpus 1 only, c4 shards its 8192 chains over the ranks")
     p.add_argument("--lib", default=None, help="(experiments) load this build of the library instead")
     p.add_argument("--chain-groups", type=int, default=None,
                    help="(experiments) chain groups on their own streams (Engine.chain_groups)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def _cpu_model():
@@ -589,6 +606,25 @@ def _ext_stream(s):
     return _STREAMS[s]
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, arrays):
+    """Write `arrays` (name -> array with the chains leading) as path/<name>.npy in float32.  Above
+    DUMP_MAX_BYTES in all, the same fixed, seeded sample of the chains is kept of every array."""
+    import numpy as np
+
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        C = next(iter(arrays.values())).shape[0]
+        keep = np.sort(np.random.RandomState(0).choice(C, max(1, C * DUMP_MAX_BYTES // total), replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def _heartbeat(t_start, period=30.0):
     """A line on stderr every `period` seconds (rank 0): the long untimed phases (adaptation of the
     configs, the CPU baselines) print nothing else for minutes, and runners that watch output take
@@ -680,7 +716,7 @@ def main():
         evs.append((a, b))
 
     pot.evaluate = timed_eval
-    parity_leg = not args.no_cpu_baseline and world == 1
+    parity_leg = args.full and not args.no_cpu_baseline and world == 1
     if parity_leg:  # decision trace of the CPU comparator's chains (parity located per leaf)
         eng.set_trace(min(args.cpu_chains, hi - lo), eng.iteration, args.steps)
     torch.cuda.synchronize()
@@ -696,19 +732,30 @@ def main():
     t1 = time.perf_counter()
     pot.evaluate = orig_eval
     elapsed = t1 - t0
-    # end-of-run exchange: cross-chain R-hat / ESS by all_reduce of per-chain
-    # statistics and the sample gather (RCCL under torch.distributed); reported, not in `value`
     from numpyro_amd import shard
 
-    torch.cuda.synchronize()
-    te0 = time.perf_counter()
     site = mcmc.get_samples(group_by_chain=True)["coefs"]
-    rhat = shard.split_gelman_rubin(site) if site.shape[1] >= 4 else None
-    ess = shard.effective_sample_size(site)
-    gathered = shard.gather_chains(site)
-    torch.cuda.synchronize()
-    end_of_run_ms = (time.perf_counter() - te0) * 1e3
     ef = mcmc.get_extra_fields(group_by_chain=True)
+    if args.dump_outputs:
+        # the last timed transition of every chain, in global chain order on rank 0
+        last = {"coefs": site[:, -1], **{k: ef[k][:, -1] for k in ("num_steps", "diverging", "potential_energy")}}
+        last = {k: shard.gather_chains(v.to(torch.float32).contiguous()).cpu().numpy() for k, v in last.items()}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last)
+    end_of_run = None
+    if args.full:
+        # end-of-run exchange: cross-chain R-hat / ESS by all_reduce of per-chain
+        # statistics and the sample gather (RCCL under torch.distributed); reported, not in `value`
+        torch.cuda.synchronize()
+        te0 = time.perf_counter()
+        rhat = shard.split_gelman_rubin(site) if site.shape[1] >= 4 else None
+        ess = shard.effective_sample_size(site)
+        gathered = shard.gather_chains(site)
+        torch.cuda.synchronize()
+        end_of_run = {"ms": (time.perf_counter() - te0) * 1e3, "gathered_chains": int(gathered.shape[0]),
+                      "max_split_rhat": float(rhat.max()) if rhat is not None else None,
+                      "min_ess": float(ess.min()), "collective": _collective(world)}
+        del gathered
     ns = ef["num_steps"].to(torch.float64)  # [C_local, steps]
     num_steps = ns.sum()
     launches = mcmc.last_run_stats["launches"]
@@ -773,10 +820,7 @@ def main():
                                         "f32 accumulation); achieved = algorithmic 4*N*D f32 FLOP per chain-leapfrog"),
                          "frac_of_f32_mfma_peak": achieved / MI355X_FP32_MFMA_PEAK_TFLOPS},
             "cpu_baseline": None,
-            "end_of_run": {"ms": end_of_run_ms, "gathered_chains": int(gathered.shape[0]),
-                           "max_split_rhat": float(rhat.max()) if rhat is not None else None,
-                           "min_ess": float(ess.min()),
-                           "collective": _collective(world)},
+            "end_of_run": end_of_run,
         }
         if parity_leg:
             k = min(args.cpu_chains, hi - lo)
@@ -786,7 +830,7 @@ def main():
             out["parity"] = cb.pop("parity")
             out["cpu_baseline"] = cb
     eng.set_trace(0, 0, 0)
-    if args.configs != "none":
+    if args.full and args.configs != "none":
         del mcmc, eng, pot, start_state
         torch.cuda.empty_cache()
         cfgs = secondary_configs(args.configs, rank, world, device,

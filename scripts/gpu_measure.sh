@@ -10,7 +10,7 @@ timeout -s KILL 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/t/w -o 
 python3 scripts/bench_traffic_summary.py $O/t > $O/traffic.json || exit 1
 rm -rf $O/t/f $O/t/w
 cat $O/traffic.json | cut -c1-400
-timeout -k 10 1100 python -u bench.py --traffic-json $O/traffic.json > $O/bench.json 2> $O/bench.err || exit 1
+timeout -k 10 1100 python -u bench.py --full --traffic-json $O/traffic.json > $O/bench.json 2> $O/bench.err || exit 1
 head -c 600 $O/bench.json; echo
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --steps 20 --warmup 5 --configs none --no-cpu-baseline --traffic-json $O/traffic.json > $O/prof.log 2>&1 || exit 1
 python3 scripts/kernel_hist.py $O/prof > $O/headline_kernel_hist.txt && cat $O/headline_kernel_hist.txt

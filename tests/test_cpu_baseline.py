@@ -115,3 +115,24 @@ def test_bench_valu_roofline_from_the_committed_profile():
     assert np.isclose(r["peak"], 1024 * 0.5 * r["clock_ghz"])
     assert 0.05 < r["frac"] < 1.0
     assert bench._valu_roofline("profiles/r05/no_such_profile.json", 1.0) is None
+
+
+def test_bench_dump_outputs_float32_and_size_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 .npy per array; above the size cap the same fixed,
+    seeded sample of the chains is kept of every array, identical from call to call."""
+    import bench
+
+    z = np.arange(40 * 3, dtype=np.float64).reshape(40, 3)
+    n = np.arange(40, dtype=np.int32)
+    bench.dump_outputs(str(tmp_path / "a"), {"z": z, "n": n})
+    za, na = np.load(tmp_path / "a" / "z.npy"), np.load(tmp_path / "a" / "n.npy")
+    assert za.dtype == na.dtype == np.float32
+    np.testing.assert_array_equal(za, z)
+    np.testing.assert_array_equal(na, n)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 160)  # 640 bytes in all: a quarter of the chains
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"z": z, "n": n})
+    zb, nb = np.load(tmp_path / "b" / "z.npy"), np.load(tmp_path / "b" / "n.npy")
+    assert zb.nbytes + nb.nbytes <= 160 and len(nb) == 10
+    np.testing.assert_array_equal(zb, z[nb.astype(int)])  # the same chains of both arrays
+    np.testing.assert_array_equal(zb, np.load(tmp_path / "c" / "z.npy"))
