@@ -94,13 +94,14 @@ _fixed_step_case = PC.fixed_step_case
 
 
 @pytest.mark.parametrize("algo", ["NUTS", "HMC"])
-@pytest.mark.parametrize("model,dim", [("logreg", 4), ("logreg", 40), ("diag_normal", 300),
-                                       ("diag_normal", 1500), ("funnel", 600), ("sv", 302),
-                                       ("bnn", 46), ("bnn", 321), ("bnn", 5038)])
+@pytest.mark.parametrize("model,dim", [("logreg", 4), ("logreg", 24), ("logreg", 40), ("logreg", 60),
+                                       ("diag_normal", 300), ("diag_normal", 1500), ("funnel", 600),
+                                       ("sv", 302), ("bnn", 46), ("bnn", 321), ("bnn", 5038)])
 def test_engine_matches_oracle_fixed_step(device, algo, model, dim):
     """No adaptation, fixed step size: every transition is a deterministic function of the
     Philox stream, so device and oracle take the same discrete path up to rounding.  D < 257
-    runs the fused step kernel (dim 4, 40, 46), SV / funnel / diagonal normal the persistent wide
+    runs the fused step kernel (dim 4, 24, 40, 46, 60: logreg's KB = 1, 2, 3 kernels and, at 64
+    chains of D = 60, its H = 0 role-split form), SV / funnel / diagonal normal the persistent wide
     kernel, the BNN the launched D-slice schedule.  Leaf-located (oracle/parity.py, the device's
     decision trace): the reference is the oracle with the potential in rounded float64; a chain
     that parts must do so at a leaf whose decision is a rounding flip of that leaf (HMC: the

@@ -9,6 +9,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import potential_cases as K
 from numpyro_amd import datasets
 from oracle import potentials as OP
 
@@ -101,8 +102,16 @@ def test_logreg_split_invariance(device):
     np.testing.assert_array_equal(g_a[200:260], g_b)
 
 
-@pytest.mark.parametrize("n_rows", [4001, 70001, 581012])
-def test_logreg_tail_forms_are_bitwise_the_full_kernel(device, n_rows):
+# D = 55 (the combined last k-block, H = 1) at every row count; D = 60 and 64 (KB = 4, H = 0: the
+# other instantiation of the role-split form and of the full kernel) and D = 24 (KB = 2, which
+# has no tail form: every launch runs the full kernel) at the smallest
+_TAIL_SHAPES = [pytest.param(4001, 55, id="4001"), pytest.param(70001, 55, id="70001"),
+                pytest.param(581012, 55, id="581012"), pytest.param(4001, 24, id="4001-D24"),
+                pytest.param(4001, 60, id="4001-D60"), pytest.param(4001, 64, id="4001-D64")]
+
+
+@pytest.mark.parametrize("n_rows,D", _TAIL_SHAPES)
+def test_logreg_tail_forms_are_bitwise_the_full_kernel(device, n_rows, D):
     """Launches over <= 256 chains run the role-split tail form; the chains of a 300-chain
     launch (the full split-bf16 kernel) get bitwise the same U / dU from it: one chain, one
     chain tile, two chain groups; ragged row counts (a short last split, padded tile rows)
@@ -110,9 +119,9 @@ def test_logreg_tail_forms_are_bitwise_the_full_kernel(device, n_rows):
     from numpyro_amd.potentials import LogisticRegression
 
     rs = np.random.RandomState(n_rows % 1000)
-    X = rs.randn(n_rows, 55).astype(np.float32)
+    X = rs.randn(n_rows, D).astype(np.float32)
     y = (rs.rand(n_rows) < 0.4).astype(np.float32)
-    Z = rs.randn(300, 55).astype(np.float32) * 0.05
+    Z = rs.randn(300, D).astype(np.float32) * 0.05
     pot = LogisticRegression(X, y)
     pe_a, g_a = _eval(pot, Z, device)
     for lo, hi in ((7, 8), (200, 232), (0, 256)):
@@ -125,9 +134,10 @@ def test_logreg_tail_forms_are_bitwise_the_full_kernel(device, n_rows):
         np.testing.assert_allclose(g_a[:8], g_r, rtol=1e-3, atol=1e-2)
 
 
-def _eval_list(pot, Z, idx, device):
+def _eval_list(pot, Z, idx, device, full=False):
     """The potential of the chains idx (a compacted active list, count = len(idx)) inside a
-    batch of every chain of Z, as the NUTS loop evaluates them: U / dU at the chains' columns."""
+    batch of every chain of Z, as the NUTS loop evaluates them: U / dU at the chains' columns
+    (full: at every chain of Z, NaN where the launch wrote nothing)."""
     import torch
 
     from numpyro_amd import native
@@ -146,11 +156,13 @@ def _eval_list(pot, Z, idx, device):
                           active_count=native.ptr(cnt), num_chains=len(idx), ldc=ldc)
     pot.evaluate(ev, native.stream_ptr())
     torch.cuda.synchronize()
+    if full:
+        return pe[:C].cpu().numpy().astype(np.float64), g[:, :C].cpu().numpy().T.astype(np.float64)
     return pe[idx].cpu().numpy().astype(np.float64), g[:, idx].cpu().numpy().T.astype(np.float64)
 
 
-@pytest.mark.parametrize("n_rows", [4001, 70001, 581012])
-def test_logreg_listed_tail_forms_are_bitwise_the_full_kernel(device, n_rows):
+@pytest.mark.parametrize("n_rows,D", _TAIL_SHAPES)
+def test_logreg_listed_tail_forms_are_bitwise_the_full_kernel(device, n_rows, D):
     """Compacted lists of <= 32 chains (the narrow form: one chain tile on four waves), 33-256
     chains (the role-split form) and a wide list (the full kernel's early-exit groups): every
     listed chain's U / dU bitwise equal to the full kernel's over the whole batch, for scattered
@@ -158,9 +170,9 @@ def test_logreg_listed_tail_forms_are_bitwise_the_full_kernel(device, n_rows):
     from numpyro_amd.potentials import LogisticRegression
 
     rs = np.random.RandomState(n_rows % 997)
-    X = rs.randn(n_rows, 55).astype(np.float32)
+    X = rs.randn(n_rows, D).astype(np.float32)
     y = (rs.rand(n_rows) < 0.4).astype(np.float32)
-    Z = rs.randn(300, 55).astype(np.float32) * 0.05
+    Z = rs.randn(300, D).astype(np.float32) * 0.05
     pot = LogisticRegression(X, y)
     pe_a, g_a = _eval(pot, Z, device)
     perm = rs.permutation(300)
@@ -370,68 +382,221 @@ def test_logreg_split_bf16_matches_f32_accuracy(device):
     assert np.median(e_g) <= 3 * max(np.median(r_g), 1e-7)
 
 
-def _bf16_rne(v):
-    """float32 -> its round-to-nearest-even bf16 value as float32 (finite inputs)."""
-    u = np.ascontiguousarray(v, np.float32).view(np.uint32).astype(np.uint64)
-    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-    return r.astype(np.uint32).view(np.float32)
+# ------------------------------------------------------------------------------------------
+# Every kernel variant the dispatch can launch, edge shapes, saturated and non-finite inputs
+# (inputs, references and checks: tests/potential_cases.py; tests/test_potential_cases.py shows
+# on the CPU that the float32 oracle passes each check used here)
+# ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D", K.LOGREG_DS)
+def test_logreg_every_variant_matches_oracle(device, D):
+    """nmx_logreg_pe_grad picks k_logreg_x3<KB, DT, H> from KB = ceil(D / 16) and H (KB = 4 and
+    D % 16 in 1..8), and for KB = 4 the role-split form k_logreg_x3_roles<4, 2, H> at <= 256
+    chains: D = 1..16 (KB 1), 17..32 (KB 2), 33..48 (KB 3), 49..56 (KB 4, H 1), 57..64 (KB 4,
+    H 0), with the exact boundaries, each at row counts of one row, one tile short and over, and
+    several tiles, at 300 chains (the full kernel) and 70 (the tail form), with O(1) logits and
+    saturated ones (|logit| up to a few thousand: exp(-|l|) = 0).  Against the float64 oracle at
+    the file's tolerances; the 70-chain launch bitwise equal to chains 0:70 of the 300-chain one
+    (potential_logreg.hip: the forms are bitwise equal; shard invariance depends on it)."""
+    from numpyro_amd.potentials import LogisticRegression
+
+    KB, DT, H, _ = K.pack_dims(D)
+    worst = [0.0, 0.0]
+    for N in K.LOGREG_NS:
+        for regime in K.REGIMES:
+            with np.errstate(over="ignore"):
+                X, y, Z, (pe_r, g_r) = K.logreg_reference(N, D, K.LOGREG_C, regime)
+            pot = LogisticRegression(X, y)
+            pe_a, g_a = _eval(pot, Z, device)
+            n = K.LOGREG_TAIL_C
+            pe_b, g_b = _eval(pot, Z[:n], device)
+            label = f"D={D} (KB={KB} H={H}) N={N} {regime}"
+            ra = K.logreg_errors(pe_a, g_a, X, y, Z, (pe_r, g_r))
+            rb = K.logreg_errors(pe_b, g_b, X, y, Z[:n], (pe_r[:n], g_r[:n]))
+            print(f"[logreg variants] {label}: error / tolerance U {ra[0]:.3f} grad {ra[1]:.3f} at C=300, "
+                  f"U {rb[0]:.3f} grad {rb[1]:.3f} at C={n}")
+            worst = [max(worst[0], ra[0], rb[0]), max(worst[1], ra[1], rb[1])]
+            K.check_logreg(pe_a, g_a, X, y, Z, (pe_r, g_r), label=label + " C=300")
+            K.check_logreg(pe_b, g_b, X, y, Z[:n], (pe_r[:n], g_r[:n]), label=label + f" C={n}")
+            np.testing.assert_array_equal(pe_b, pe_a[:n], err_msg=label)
+            np.testing.assert_array_equal(g_b, g_a[:n], err_msg=label)
+    print(f"[logreg variants] D={D}: worst error / tolerance U {worst[0]:.3f} grad {worst[1]:.3f}")
 
 
-def test_logreg_packed_split_is_bitwise_the_numpy_split(device):
+@pytest.mark.parametrize("N,D", K.PACK_SHAPES)
+def test_logreg_packed_split_is_bitwise_the_numpy_split(device, N, D):
     """nmx_logreg_pack's tiles hold each X value as three bf16 terms v1 = bf16(v),
     v2 = bf16(v - v1), v3 = bf16(v - v1 - v2), round to nearest even (potential_logreg.hip
-    split3, converted in value pairs): bit-exact against a NumPy restatement of that split,
-    in both operand layouts (GEMM1 A pieces: X[32 t + r][16 kb + 8 h + j]; GEMM2 B pieces:
-    X[16 s + 8 (j >> 2) + 4 h + (j & 3)][32 dt + r]) and in the combined last-k-block pieces
-    of D % 16 <= 8 (every lane X[32 t + r][48 + j], terms (1 | 2) and (3 | 1) by lane half),
-    padded rows and columns zero."""
+    split3, converted in value pairs): bit-exact against a NumPy restatement of that split
+    (potential_cases.expected_pack), in both operand layouts (GEMM1 A pieces: X[32 t + r]
+    [16 kb + 8 h + j]; GEMM2 B pieces: X[16 s + 8 (j >> 2) + 4 h + (j & 3)][32 dt + r]), in the
+    combined last-k-block pieces of H = 1 (every lane X[32 t + r][48 + j], terms (1 | 2) and
+    (3 | 1) by lane half) and in the label piece (y - 1/2 in lanes 0..7), padded rows and columns
+    zero; for every (KB, DT, H) of x3_kb / x3_dt / x3_h: D = 55 (4, 2, 1), 60 and 64 (4, 2, 0),
+    49 and 56 (the ends of H = 1), 24 (2, 1, 0), 16 and 1 (1, 1, 0); one row, one tile, three."""
     import torch
 
     from numpyro_amd.potentials import LogisticRegression
 
     rs = np.random.RandomState(11)
-    N, D = 77, 55
     X = (rs.randn(N, D) * np.exp(rs.randn(N, D) * 3)).astype(np.float32)  # wide exponent range
-    X[3, :7] = [0.0, -0.0, 1e-30, -3e-30, 65504.0, 1.0 + 2 ** -23, -(1.0 + 2 ** -9)]
+    special = [0.0, -0.0, 1e-30, -3e-30, 65504.0, 1.0 + 2 ** -23, -(1.0 + 2 ** -9)][:D]
+    X[min(3, N - 1), :len(special)] = special
     y = (rs.rand(N) < 0.5).astype(np.float32)
     pot = LogisticRegression(X, y)
     pot.bind(64, 64, device)
     raw = pot.packed.view(torch.uint8).cpu().numpy()
-    KB, DT = (D + 15) // 16, (D + 31) // 32
-    H = 1  # D = 55: combined last k-block (potential_logreg.hip x3_h)
-    NP = 3 * KB + 2 * H + 6 * DT + 1
+    KB, DT, H, NP = K.pack_dims(D)
     nt = (N + 31) // 32
-    tiles = raw[512:512 + nt * NP * 1024].view(np.uint16).reshape(nt, NP, 64, 8)
-    got = (tiles.astype(np.uint32) << 16).view(np.float32)  # bf16 bits -> float32 values
-
-    Xp = np.zeros((nt * 32, 64), np.float32)
-    Xp[:N, :D] = X
-    t1 = _bf16_rne(Xp)
-    e1 = Xp - t1
-    t2 = _bf16_rne(e1)
-    t3 = _bf16_rne(e1 - t2)
-    planes = [t1, t2, t3]
-    lane = np.arange(64)
-    r, h = lane & 31, lane >> 5
-    j = np.arange(8)
-    for t in range(nt):
-        for p in range(3):
-            for kb in range(KB):
-                rows = 32 * t + r[:, None]
-                cols = 16 * kb + 8 * h[:, None] + j[None, :]
-                want = planes[p][rows, cols]
-                np.testing.assert_array_equal(got[t, p * KB + kb].view(np.uint32), want.view(np.uint32))
-            for dt in range(DT):
-                for s in range(2):
-                    rows = 32 * t + 16 * s + 8 * (j[None, :] >> 2) + 4 * h[:, None] + (j[None, :] & 3)
-                    cols = 32 * dt + r[:, None] + 0 * j[None, :]
-                    want = planes[p][rows, cols]
-                    piece = 3 * KB + 2 * H + p * 2 * DT + 2 * dt + s
-                    np.testing.assert_array_equal(got[t, piece].view(np.uint32), want.view(np.uint32))
-    rows = 32 * np.arange(nt)[:, None, None] + r[None, :, None]
-    cols = 16 * (KB - 1) + j[None, None, :] + 0 * rows
-    for cp, (ph0, ph1) in enumerate([(0, 1), (2, 0)]):
-        want = np.where((h == 0)[None, :, None], planes[ph0][rows, cols], planes[ph1][rows, cols])
-        np.testing.assert_array_equal(got[:, 3 * KB + cp].view(np.uint32), want.view(np.uint32))
+    assert raw.size == 512 + nt * NP * 1024  # nmx_logreg_packed_bytes: the column terms, then the tiles
+    got = raw[512:].view(np.uint16).reshape(nt, NP, 64, 8)
+    want, (t1, t2, t3), Xp = K.expected_pack(X, y)
+    assert want.shape == got.shape
+    for p in range(3):
+        for kb in range(KB):
+            np.testing.assert_array_equal(got[:, p * KB + kb], want[:, p * KB + kb], err_msg=f"A piece term {p} kb {kb}")
+        for q in range(2 * DT):
+            piece = 3 * KB + 2 * H + p * 2 * DT + q
+            np.testing.assert_array_equal(got[:, piece], want[:, piece], err_msg=f"B piece term {p} dt {q >> 1} s {q & 1}")
+    for cp in range(2 * H):
+        np.testing.assert_array_equal(got[:, 3 * KB + cp], want[:, 3 * KB + cp], err_msg=f"combined piece {cp}")
+    np.testing.assert_array_equal(got[:, NP - 1], want[:, NP - 1], err_msg="label piece")
+    np.testing.assert_array_equal(got, want)
     # the three terms represent every value to within 2^-24 relative (f32 rounding unit)
     assert np.all(np.abs((t1.astype(np.float64) + t2 + t3) - Xp) <= 2.0 ** -24 * np.abs(Xp) + 1e-45)
+
+
+def _nonfinite_case(which):
+    """(potential, finite Z [70, D]) of test_nonfinite_chain_is_rejected_and_contained."""
+    from numpyro_amd import potentials as P
+
+    C = 70
+    if which.startswith("logreg"):
+        X, y, Z = K.logreg_case(257, int(which[6:]), C, "unit")
+        return P.LogisticRegression(X, y), Z
+    if which == "sv":
+        r, Z = K.sv_case(65, C)
+        return P.StochasticVolatility(r), Z
+    if which == "funnel":
+        return P.Funnel(66), K.funnel_case(66, C)
+    if which == "funnel_nc":
+        return P.FunnelNonCentered(66), K.funnel_case(66, C)
+    X, Y = datasets.bnn_data(N=37, D_X=3)
+    pot = P.BNN(X, Y, 16)
+    rs = np.random.RandomState(16)
+    Z = (0.5 * rs.randn(C, pot.dim)).astype(np.float32)
+    Z[:, 0] = rs.uniform(-1.0, 2.0, C)
+    return pot, Z
+
+
+@pytest.mark.parametrize("which", ["logreg55", "logreg60", "sv", "funnel", "funnel_nc", "bnn"])
+def test_nonfinite_chain_is_rejected_and_contained(device, which):
+    """A chain whose coordinates hold NaN or +-inf gets U = NaN or +inf -- never -inf and never a
+    finite value: the tree builder turns a NaN energy into +inf (a rejected proposal), so a
+    U = -inf would be accepted as a perfect one -- and its neighbours in the same 32-chain MFMA
+    tile and 64-chain group (chains 5, 37 in group 0, chain 64 in group 1) get bitwise the U and
+    dU of the launch where those three chains hold finite values."""
+    pot, Z = _nonfinite_case(which)
+    D = Z.shape[1]
+    bad = Z.copy()
+    bad[5, 0] = np.nan
+    bad[37, D - 1] = np.inf
+    bad[64, D // 2] = -np.inf
+    pe_f, g_f = _eval(pot, Z, device)
+    pe_b, g_b = _eval(pot, bad, device)
+    assert np.all(np.isfinite(pe_f)) and np.all(np.isfinite(g_f))
+    for c in (5, 37, 64):
+        print(f"[non-finite] {which}: chain {c} U = {pe_b[c]}")
+        assert np.isnan(pe_b[c]) or pe_b[c] == np.inf, f"chain {c}: U = {pe_b[c]}"
+    others = np.setdiff1d(np.arange(Z.shape[0]), [5, 37, 64])
+    np.testing.assert_array_equal(pe_b[others], pe_f[others])
+    np.testing.assert_array_equal(g_b[others], g_f[others])
+
+
+_WIDE_SHAPES = [("sv", T) for T in K.SV_TS] + [(m, d) for m in ("funnel", "funnel_nc") for d in K.FUNNEL_DIMS]
+
+
+def _wide_potential(model, size, data):
+    from numpyro_amd import potentials as P
+
+    return {"sv": lambda: P.StochasticVolatility(data), "funnel": lambda: P.Funnel(size),
+            "funnel_nc": lambda: P.FunnelNonCentered(size)}[model]()
+
+
+@pytest.mark.parametrize("model,size", _WIDE_SHAPES)
+def test_wide_models_at_slice_and_group_edges(device, model, size):
+    """potential_wide.hip splits the rows into 64-row slices and the chains into 64-chain groups:
+    SV at T = 2 (the smallest the ABI accepts: both stencil guards on every row), 3, 63, 64, 65,
+    129, 300 and the funnels at dim = 2, 3, 64, 65, 66, 130 (rows = 1, 2, 63, 64, 65, 129), one
+    chain and 65 (a second group of one).  SV inputs span nu / 2 in [0.025, 55] and q from 1e-15
+    (the u == 1 branch) to 1e10.  The errors against float64 stay within 4x the float32 oracle's
+    (floor 4 x 2^-23: potential_cases.check_wide_vs_f32), inside the file's existing tolerances
+    as the outer bound.  SV's U and gradient and the centred funnel's gradient are differences of
+    float32 row sums that cancel, which no float32 evaluation holds to 4x an oracle that rounds a
+    float64 result once (measured on the device at 65 chains: SV U up to 164x at T = 64, gradient
+    15x; funnel gradient 31x at dim 130; a plain NumPy float32 evaluation: 167x, 11x, 76x --
+    potential_cases.WIDE_F32_LIMITED); those three are held to the existing tolerances and to 4x
+    that plain float32 evaluation's error, the ratio to the oracle printed.  At one size per model a scattered compacted list of 9 chains gives
+    bitwise the dense launch's values and leaves the other chains' NaN fill in place."""
+    for C in K.WIDE_CS:
+        data, Z, ref64, ref32 = K.wide_reference(model, size, C)
+        pot = _wide_potential(model, size, data)
+        pe, g = _eval(pot, Z, device)
+        if model == "sv":
+            K.check_sv_outer(pe, g, ref64)
+        else:
+            K.check_funnel_outer(pe, g, ref64, centred=model == "funnel")
+        limited = K.WIDE_F32_LIMITED[model]
+        K.check_wide_vs_f32(pe, g, ref64, ref32, Z, label=f"{model} size={size} C={C}", limited=limited,
+                            plain32=K.wide_plain_f32(model, size, C) if any(limited) else None)
+        if C == 65 and size in (65, 66):
+            idx = np.array([64, 3, 17, 0, 63, 31, 32, 40, 9])
+            pe_l, g_l = _eval_list(pot, Z, idx, device, full=True)
+            np.testing.assert_array_equal(pe_l[idx], pe[idx])
+            np.testing.assert_array_equal(g_l[idx], g[idx])
+            rest = np.setdiff1d(np.arange(C), idx)
+            assert np.all(np.isnan(pe_l[rest])) and np.all(np.isnan(g_l[rest]))
+
+
+def test_torch_potential_evaluate_matches_oracle(device):
+    """TorchPotential.evaluate (the generic path: torch.func on the gathered chains, results
+    scattered back) on a diagonal normal written as a function of a site dict, D = 5 over two
+    sites: U and dU against the float64 oracle to test_diag_normal's tolerances -- dense, with a
+    phase array (only LEAF chains evaluated) and on a scattered compacted list; chains that are
+    not selected keep their NaN fill."""
+    import torch
+
+    from numpyro_amd import native
+    from numpyro_amd.potentials import TorchPotential
+
+    mu = np.array([0.5, -1.0, 2.0, 0.0, 1.5], np.float32)
+    sd = np.array([1.0, 0.5, 2.0, 1.5, 0.8], np.float32)
+    mu_t, sd_t = torch.from_numpy(mu).to(device), torch.from_numpy(sd).to(device)
+
+    def fn(z):  # sites in sorted order: "a" holds coordinates 0..1, "b" 2..4
+        return 0.5 * (((z["a"] - mu_t[:2]) / sd_t[:2]) ** 2).sum() + 0.5 * (((z["b"] - mu_t[2:]) / sd_t[2:]) ** 2).sum()
+
+    pot = TorchPotential(fn, {"b": torch.zeros(3), "a": torch.zeros(2)})
+    assert pot.dim == 5 and [s[0] for s in pot.sites] == ["a", "b"]
+    C = 70
+    Z = (2.0 * np.random.RandomState(5).randn(C, 5)).astype(np.float32)
+    ref = OP.IsoNormal(mu, sd)
+    out = [ref.pe_grad(z.astype(np.float64)) for z in Z]
+    pe_r, g_r = np.array([o[0] for o in out]), np.stack([o[1] for o in out])
+
+    def close(pe, g, sel):
+        np.testing.assert_allclose(pe[sel], pe_r[sel], rtol=1e-5, atol=1e-6)
+        np.testing.assert_allclose(g[sel], g_r[sel], rtol=1e-5, atol=1e-6)
+
+    pe, g = _eval(pot, Z, device)
+    close(pe, g, np.arange(C))
+    phase = np.zeros(C, np.int32)
+    phase[[1, 2, 30, 63, 64, 69]] = native.PH_LEAF
+    pe, g = _eval(pot, Z, device, phase=phase)
+    on = phase == native.PH_LEAF
+    close(pe, g, on)
+    assert np.all(np.isnan(pe[~on])) and np.all(np.isnan(g[~on]))
+    idx = np.array([64, 3, 17, 0, 63, 31, 32, 40, 9])
+    pe, g = _eval_list(pot, Z, idx, device, full=True)
+    close(pe, g, idx)
+    rest = np.setdiff1d(np.arange(C), idx)
+    assert np.all(np.isnan(pe[rest])) and np.all(np.isnan(g[rest]))
