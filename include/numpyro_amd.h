@@ -352,6 +352,56 @@ int nmx_pe_bnn_rows(const float* X, const float* Y, int N, int Dx, int H, const 
 /* Workspace of nmx_pe_bnn: the evaluated chains' z and gradient transposed to rows. */
 size_t nmx_pe_bnn_workspace_bytes(int Dx, int H, int num_chains);
 
+/* ---- program potential: the generic path of the model front end (numpyro/infer/util.py:
+ *      546-611 potential_fn_gen + jax.value_and_grad).  A traced model's U(z) is lowered
+ *      (numpyro_amd/program.py) to a straight-line program over f32 vectors; one kernel
+ *      evaluates it and its reverse-mode adjoint for every evaluated chain.
+ *
+ * Slots: each evaluated position owns num_slots f32 values and as many adjoints.  Slots
+ * [0, dim) hold z (unconstrained); every op defines the next free slots, in order (single
+ * assignment), so an operand always precedes its use.  The last op defines one slot: U.
+ *
+ * An op is NMX_OP_WORDS int32: { opcode, dst, a, b, n, sa, sb, aux }.
+ *   elementwise ops (n elements, i < n): dst[i] = f(a[i * sa], b[i * sb]); an operand
+ *     reference >= 0 is a slot, < 0 the constant-pool offset ~ref; strides are 0
+ *     (broadcast scalar) or 1; unary ops read a slot, binary ops at least one.
+ *   NMX_OP_REDUCE_SUM: dst[0] = sum_{i < n} a[i].
+ *   NMX_OP_GATHER: dst[i] = a[index[aux + i]], i < n, the source being b slots long; the
+ *     index pool holds at aux: n source indices, then the transposed (CSR) form for the
+ *     adjoint: b + 1 row starts into n positions of dst, grouped by source element.
+ *   NMX_OP_MATVEC: dst[i] = sum_k M[i][k] a[k], i < n, k < aux; M [n][aux] row-major at
+ *     constant offset ~b, followed by its transpose [aux][n].
+ * Sums run in an order fixed by the program alone (per-lane strided partial sums, then a
+ * fixed butterfly over the 64 lanes), with no atomics: U and the gradient are bitwise
+ * independent of chain count, position, ldc, list order. ---- */
+enum nmx_opcode {
+  NMX_OP_NEG = 0, NMX_OP_EXP, NMX_OP_LOG, NMX_OP_SQRT, NMX_OP_TANH, NMX_OP_LOG1P, NMX_OP_SQUARE,
+  NMX_OP_SOFTPLUS, NMX_OP_LGAMMA,                                       /* unary */
+  NMX_OP_ADD, NMX_OP_SUB, NMX_OP_MUL, NMX_OP_DIV, NMX_OP_POW,           /* binary */
+  NMX_OP_REDUCE_SUM, NMX_OP_GATHER, NMX_OP_MATVEC,
+  NMX_NUM_OPCODES
+};
+#define NMX_OP_WORDS 8
+
+typedef struct nmx_program {
+  const int32_t* ops;    /* [num_ops][NMX_OP_WORDS] */
+  const float* consts;   /* [num_consts] */
+  const int32_t* index;  /* [num_index] (may be NULL when num_index = 0) */
+  int32_t num_ops, num_slots, num_consts, num_index;
+  int32_t dim;           /* coordinates of z: slots [0, dim) */
+} nmx_program;
+
+/* Validate a program whose arrays are in HOST memory: every opcode, count, stride, slot,
+ * constant and index-pool reference and every gather index against the pool and slot sizes.
+ * Needs no GPU.  NMX_ERR_INVALID with nmx_last_error naming the op otherwise; only a program
+ * that passed may be uploaded and given to nmx_pe_program. */
+int nmx_program_check(const nmx_program* host_program);
+/* Workspace of nmx_pe_program: values and adjoints of ldc positions. */
+size_t nmx_pe_program_workspace_bytes(int num_slots, int ldc);
+/* One launch: forward, reverse, pe and grad of every evaluated chain.  `program` holds DEVICE
+ * arrays of a program nmx_program_check accepted. */
+int nmx_pe_program(const nmx_program* program, const nmx_eval_batch* ev, void* workspace, void* stream);
+
 /* Logistic regression (examples/covtype.py:66-71): coefs ~ N(0,1)^D,
  * obs ~ BernoulliLogits(X @ coefs).  X is first packed (row tiles with the label in a pad
  * column); U and dU are computed by two f32 MFMA GEMMs per 32-row tile

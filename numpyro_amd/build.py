@@ -43,14 +43,16 @@ COMMON_FLAGS = [
 # * the covtype kernel's epilogue and residual split stay scalar VALU (the SLP vectorizer would
 #   pair them into v_pk_*_f32, which issue slower beside MFMAs on gfx950; potential_logreg.hip
 #   x3_epi_one);
-# * no floating-point contraction in the step kernels and the small models' potentials: the
+# * no floating-point contraction in the step kernels, the small models' potentials and the
+#   program potential (a per-chain body in a header, nmx_program.h, like the small models): the
 #   same device function is inlined into several kernels (the launched step, the persistent
 #   schedule, the sync / async schedules), and whether the backend fuses a * b + c into an FMA
 #   depends on each kernel's code generation -- with contraction off every kernel rounds every
 #   product, so the schedules stay bitwise identical (and round like the NumPy oracle)
 FILE_FLAGS = {"potential_logreg.hip": ["-fno-slp-vectorize"],
               "nuts.hip": ["-ffp-contract=off"],
-              "potential_small.hip": ["-ffp-contract=off"]}
+              "potential_small.hip": ["-ffp-contract=off"],
+              "potential_program.hip": ["-ffp-contract=off"]}
 
 
 def _headers():

@@ -1,0 +1,227 @@
+// Per-position body of the program potential (include/numpyro_amd.h "program potential"): one
+// wave evaluates a straight-line program and its reverse-mode adjoint for one chain.  Kept as a
+// struct, like the small models (nmx_small_models.h), so another kernel can inline the same body.
+//
+// Lane mapping: element i of every value is computed, and its adjoint accumulated, by lane
+// i % 64 (scalars by lane 0).  An op whose operands are read at the element it writes needs no
+// synchronisation; the ops that read across lanes (reduce, gather, matvec, a broadcast scalar
+// slot) are preceded by a workgroup barrier.  Every sum has an order fixed by the program:
+// a lane adds its elements i = lane, lane + 64, ... in order, the 64 partial sums are combined by
+// a butterfly (every lane ends with the same bits).  No atomics.
+#pragma once
+#include <math.h>
+
+#include "nmx_common.h"
+
+__device__ __forceinline__ float nmx_wave_sum(float x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
+  return x;
+}
+
+// digamma(x), x > 0: the recurrence psi(x) = psi(x + 1) - 1/x up to x >= 8 (at most 8 steps; a
+// non-finite or non-positive x leaves the loop by its bound), then the asymptotic series
+// ln x - 1/(2x) - 1/(12x^2) + 1/(120x^4) - 1/(252x^6) (next term 1/(240 x^8) < 3e-9 at x = 8).
+__device__ __forceinline__ float nmx_digammaf(float x) {
+  float shift = 0.0f;
+  for (int k = 0; k < 8 && x < 8.0f; ++k) {
+    shift += 1.0f / x;
+    x += 1.0f;
+  }
+  const float r = 1.0f / x, r2 = r * r;
+  const float tail = r2 * (1.0f / 12 - r2 * (1.0f / 120 - r2 * (1.0f / 252)));
+  return logf(x) - 0.5f * r - tail - shift;
+}
+
+struct NmxOp {
+  int op, dst, a, b, n, sa, sb, aux;
+};
+
+struct NmxProgram {
+  nmx_program p;
+  float* ws;  // [position][2][num_slots]: values, adjoints
+
+  __device__ __forceinline__ NmxOp load(int k) const {
+    const int32_t* w = p.ops + (size_t)k * NMX_OP_WORDS;
+    return NmxOp{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7]};
+  }
+  __device__ __forceinline__ float operand(const float* v, int ref, int i) const {
+    NMX_DCHECK(ref >= 0 ? ref + i < p.num_slots : ~ref + i < p.num_consts);
+    return ref >= 0 ? v[ref + i] : p.consts[~ref + i];
+  }
+  // the ops that read values other lanes wrote
+  __device__ __forceinline__ static bool crosses(const NmxOp& o) { return o.op >= NMX_OP_REDUCE_SUM; }
+  __device__ __forceinline__ static bool wave_per_row(int rows, int cols) { return rows < 64 && cols >= 64; }
+
+  __device__ __forceinline__ static float fwd(int op, float x, float y) {
+    switch (op) {
+      case NMX_OP_NEG: return -x;
+      case NMX_OP_EXP: return expf(x);
+      case NMX_OP_LOG: return logf(x);
+      case NMX_OP_SQRT: return sqrtf(x);
+      case NMX_OP_TANH: return tanhf(x);
+      case NMX_OP_LOG1P: return log1pf(x);
+      case NMX_OP_SQUARE: return x * x;
+      case NMX_OP_SOFTPLUS: return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x)));
+      case NMX_OP_LGAMMA: return lgammaf(x);
+      case NMX_OP_ADD: return x + y;
+      case NMX_OP_SUB: return x - y;
+      case NMX_OP_MUL: return x * y;
+      case NMX_OP_DIV: return x / y;
+      default: return powf(x, y);  // NMX_OP_POW
+    }
+  }
+  // adjoints of the operands from the result's (gd), the operands and the result
+  __device__ __forceinline__ static void rev(int op, float gd, float x, float y, float out, float& da, float& db) {
+    db = 0.0f;
+    switch (op) {
+      case NMX_OP_NEG: da = -gd; break;
+      case NMX_OP_EXP: da = gd * out; break;
+      case NMX_OP_LOG: da = gd / x; break;
+      case NMX_OP_SQRT: da = gd * 0.5f / out; break;
+      case NMX_OP_TANH: da = gd * (1.0f - out * out); break;
+      case NMX_OP_LOG1P: da = gd / (1.0f + x); break;
+      case NMX_OP_SQUARE: da = gd * (2.0f * x); break;
+      case NMX_OP_SOFTPLUS: da = gd / (1.0f + expf(-x)); break;
+      case NMX_OP_LGAMMA: da = gd * nmx_digammaf(x); break;
+      case NMX_OP_ADD: da = gd; db = gd; break;
+      case NMX_OP_SUB: da = gd; db = -gd; break;
+      case NMX_OP_MUL: da = gd * y; db = gd * x; break;
+      case NMX_OP_DIV: da = gd / y; db = -(gd * out) / y; break;
+      default: da = gd * (y * powf(x, y - 1.0f)); db = gd * (out * logf(x)); break;  // NMX_OP_POW
+    }
+  }
+
+  __device__ __forceinline__ void forward(const NmxOp& o, float* v, int lane) const {
+    if (o.op < NMX_OP_REDUCE_SUM) {
+      const bool binary = o.op >= NMX_OP_ADD;
+      for (int i = lane; i < o.n; i += 64) {
+        const float x = operand(v, o.a, i * o.sa);
+        const float y = binary ? operand(v, o.b, i * o.sb) : 0.0f;
+        v[o.dst + i] = fwd(o.op, x, y);
+      }
+    } else if (o.op == NMX_OP_REDUCE_SUM) {
+      float s = 0.0f;
+      for (int i = lane; i < o.n; i += 64) s += v[o.a + i];
+      s = nmx_wave_sum(s);
+      if (lane == 0) v[o.dst] = s;
+    } else if (o.op == NMX_OP_GATHER) {
+      const int32_t* idx = p.index + o.aux;
+      for (int i = lane; i < o.n; i += 64) v[o.dst + i] = v[o.a + idx[i]];
+    } else {  // NMX_OP_MATVEC
+      const int K = o.aux;
+      const float* M = p.consts + ~o.b;
+      const float* Mt = M + (size_t)o.n * K;
+      if (wave_per_row(o.n, K)) {
+        for (int i = 0; i < o.n; ++i) {
+          float s = 0.0f;
+          for (int k = lane; k < K; k += 64) s += M[(size_t)i * K + k] * v[o.a + k];
+          s = nmx_wave_sum(s);
+          if (lane == (i & 63)) v[o.dst + i] = s;
+        }
+      } else {
+        for (int i = lane; i < o.n; i += 64) {
+          float s = 0.0f;
+          for (int k = 0; k < K; ++k) s += Mt[(size_t)k * o.n + i] * v[o.a + k];
+          v[o.dst + i] = s;
+        }
+      }
+    }
+  }
+
+  __device__ __forceinline__ void reverse(const NmxOp& o, const float* v, float* g, int lane) const {
+    if (o.op < NMX_OP_REDUCE_SUM) {
+      const bool binary = o.op >= NMX_OP_ADD;
+      const bool ga = o.a >= 0, gb = binary && o.b >= 0;
+      float pa = 0.0f, pb = 0.0f;  // adjoint of a broadcast scalar: this lane's part
+      for (int i = lane; i < o.n; i += 64) {
+        const float x = operand(v, o.a, i * o.sa);
+        const float y = binary ? operand(v, o.b, i * o.sb) : 0.0f;
+        float da, db;
+        rev(o.op, g[o.dst + i], x, y, v[o.dst + i], da, db);
+        if (ga) {
+          if (o.sa) g[o.a + i] += da;
+          else pa += da;
+        }
+        if (gb) {
+          if (o.sb) g[o.b + i] += db;
+          else pb += db;
+        }
+      }
+      if (ga && !o.sa) {
+        pa = nmx_wave_sum(pa);
+        if (lane == 0) g[o.a] += pa;
+      }
+      if (gb && !o.sb) {
+        pb = nmx_wave_sum(pb);
+        if (lane == 0) g[o.b] += pb;
+      }
+    } else if (o.op == NMX_OP_REDUCE_SUM) {
+      const float gd = g[o.dst];
+      for (int i = lane; i < o.n; i += 64) g[o.a + i] += gd;
+    } else if (o.op == NMX_OP_GATHER) {
+      // segmented sum over the transposed index: source element j collects the results that read it
+      const int32_t* start = p.index + o.aux + o.n;
+      const int32_t* who = start + o.b + 1;
+      for (int j = lane; j < o.b; j += 64) {
+        float s = 0.0f;
+        for (int t = start[j]; t < start[j + 1]; ++t) s += g[o.dst + who[t]];
+        g[o.a + j] += s;
+      }
+    } else {  // NMX_OP_MATVEC: g_a += M^T g_dst
+      const int K = o.aux;
+      const float* M = p.consts + ~o.b;
+      const float* Mt = M + (size_t)o.n * K;
+      if (wave_per_row(K, o.n)) {
+        for (int k = 0; k < K; ++k) {
+          float s = 0.0f;
+          for (int i = lane; i < o.n; i += 64) s += Mt[(size_t)k * o.n + i] * g[o.dst + i];
+          s = nmx_wave_sum(s);
+          if (lane == (k & 63)) g[o.a + k] += s;
+        }
+      } else {
+        for (int k = lane; k < K; k += 64) {
+          float s = 0.0f;
+          for (int i = 0; i < o.n; ++i) s += M[(size_t)i * K + k] * g[o.dst + i];
+          g[o.a + k] += s;
+        }
+      }
+    }
+  }
+
+  // a broadcast scalar slot is read by every lane and was written by lane 0
+  __device__ __forceinline__ static bool reads_scalar_slot(const NmxOp& o) {
+    if (o.op >= NMX_OP_REDUCE_SUM || o.n == 1) return false;
+    return (o.a >= 0 && !o.sa) || (o.op >= NMX_OP_ADD && o.b >= 0 && !o.sb);
+  }
+  // z slots are referenced at any offset: their adjoints have no fixed lane
+  __device__ __forceinline__ bool touches_z(const NmxOp& o) const {
+    return (o.a >= 0 && o.a < p.dim) || (o.op >= NMX_OP_ADD && o.op < NMX_OP_REDUCE_SUM && o.b >= 0 && o.b < p.dim);
+  }
+
+  // chain c at position pos of the batch; called by all 64 lanes of a one-wave workgroup
+  __device__ __forceinline__ void operator()(const nmx_eval_batch& ev, int c, int pos, int lane) const {
+    const int S = p.num_slots, D = p.dim;
+    NMX_DCHECK(pos >= 0 && pos < ev.ldc && c >= 0 && c < ev.ldc);
+    float* v = ws + (size_t)pos * 2 * S;
+    float* g = v + S;
+    for (int i = lane; i < S; i += 64) g[i] = 0.0f;
+    for (int d = lane; d < D; d += 64) v[d] = ev.z[(size_t)d * ev.ldc + c];
+    __syncthreads();
+    for (int k = 0; k < p.num_ops; ++k) {
+      const NmxOp o = load(k);
+      if (crosses(o) || reads_scalar_slot(o)) __syncthreads();
+      forward(o, v, lane);
+    }
+    __syncthreads();
+    if (lane == 0) g[S - 1] = 1.0f;
+    for (int k = p.num_ops - 1; k >= 0; --k) {
+      const NmxOp o = load(k);
+      if (crosses(o) || touches_z(o)) __syncthreads();
+      reverse(o, v, g, lane);
+    }
+    __syncthreads();
+    for (int d = lane; d < D; d += 64) ev.grad[(size_t)d * ev.ldc + c] = g[d];
+    if (lane == 0) ev.pe[c] = v[S - 1];
+  }
+};

@@ -1,0 +1,125 @@
+// Program potential: the generic path of the model front end.  One wave (a 64-thread
+// workgroup) per evaluated position interprets the traced model's program and its adjoint
+// (per-position body in nmx_program.h); nmx_program_check validates a program on the host
+// before it may be uploaded, so every address the kernel forms comes from checked fields.
+#include <math.h>
+
+#include <vector>
+
+#include "nmx_api_internal.h"
+#include "nmx_common.h"
+#include "nmx_program.h"
+
+namespace {
+
+__global__ __launch_bounds__(64) void k_program(NmxProgram prog, nmx_eval_batch ev) {
+  const int pos = blockIdx.x;
+  const int c = nmx_eval_chain(ev, pos);
+  if (c < 0) return;
+  prog(ev, c, pos, threadIdx.x);
+}
+
+const char* const OP_NAMES[NMX_NUM_OPCODES] = {"neg", "exp", "log", "sqrt", "tanh", "log1p", "square", "softplus",
+                                               "lgamma", "add", "sub", "mul", "div", "pow", "reduce_sum",
+                                               "gather", "matvec"};
+
+}  // namespace
+
+extern "C" int nmx_program_check(const nmx_program* hp) {
+  if (!hp || !hp->ops || !hp->consts) return nmx_fail(NMX_ERR_INVALID, "program has NULL arrays");
+  const nmx_program& p = *hp;
+  if (p.num_ops <= 0 || p.dim <= 0 || p.num_slots <= p.dim || p.num_consts < 0 || p.num_index < 0)
+    return nmx_fail(NMX_ERR_INVALID, "program sizes: %d ops, %d slots, dim %d, %d constants, %d indices", p.num_ops,
+                    p.num_slots, p.dim, p.num_consts, p.num_index);
+  if (p.num_index > 0 && !p.index) return nmx_fail(NMX_ERR_INVALID, "program has a NULL index pool");
+  // length of the value defined at each slot (0: not the start of a value)
+  std::vector<int32_t> def_len((size_t)p.num_slots, 0);
+  int64_t cursor = p.dim;
+  for (int k = 0; k < p.num_ops; ++k) {
+    const int32_t* w = p.ops + (size_t)k * NMX_OP_WORDS;
+    const int op = w[0], dst = w[1], a = w[2], b = w[3], n = w[4], sa = w[5], sb = w[6], aux = w[7];
+    if (op < 0 || op >= NMX_NUM_OPCODES) return nmx_fail(NMX_ERR_INVALID, "op %d: bad opcode %d", k, op);
+    const char* nm = OP_NAMES[op];
+    if (n <= 0) return nmx_fail(NMX_ERR_INVALID, "op %d (%s): count %d <= 0", k, nm, n);
+    const int64_t dst_len = op == NMX_OP_REDUCE_SUM ? 1 : n;
+    if (dst != cursor || cursor + dst_len > p.num_slots)
+      return nmx_fail(NMX_ERR_INVALID, "op %d (%s): destination slot %d (+%lld) out of range or out of order "
+                      "(next free slot %lld of %d)", k, nm, dst, (long long)dst_len, (long long)cursor, p.num_slots);
+    // a slot operand of `len` elements: inside z, or the start of an earlier op's value
+    auto slot_ok = [&](int ref, int64_t len) {
+      if (ref < 0 || ref >= dst) return false;
+      if (ref < p.dim) return ref + len <= p.dim;
+      return def_len[ref] >= len;
+    };
+    auto const_ok = [&](int ref, int64_t len) { return ref < 0 && (int64_t)~ref + len <= p.num_consts; };
+    if (op < NMX_OP_REDUCE_SUM) {
+      const bool binary = op >= NMX_OP_ADD;
+      if ((sa != 0 && sa != 1) || (sb != 0 && sb != 1))
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): strides %d, %d not 0 or 1", k, nm, sa, sb);
+      const int64_t la = sa ? n : 1, lb = sb ? n : 1;
+      if (a >= 0 ? !slot_ok(a, la) : (!binary || !const_ok(a, la)))
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): first operand %s %d (x%lld) out of range", k, nm,
+                        a >= 0 ? "slot" : "constant", a >= 0 ? a : ~a, (long long)la);
+      if (binary) {
+        if (b >= 0 ? !slot_ok(b, lb) : !const_ok(b, lb))
+          return nmx_fail(NMX_ERR_INVALID, "op %d (%s): second operand %s %d (x%lld) out of range", k, nm,
+                          b >= 0 ? "slot" : "constant", b >= 0 ? b : ~b, (long long)lb);
+        if (a < 0 && b < 0) return nmx_fail(NMX_ERR_INVALID, "op %d (%s): both operands constant", k, nm);
+      }
+    } else if (op == NMX_OP_REDUCE_SUM) {
+      if (!slot_ok(a, n)) return nmx_fail(NMX_ERR_INVALID, "op %d (%s): operand slot %d (x%d) out of range", k, nm, a, n);
+    } else if (op == NMX_OP_GATHER) {
+      if (b <= 0 || !slot_ok(a, b))
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): source slot %d of length %d out of range", k, nm, a, b);
+      if (aux < 0 || (int64_t)aux + 2 * (int64_t)n + b + 1 > p.num_index)
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): index reference %d (+%lld) outside the pool of %d", k, nm, aux,
+                        (long long)(2 * (int64_t)n + b + 1), p.num_index);
+      const int32_t* idx = p.index + aux;
+      const int32_t* start = idx + n;
+      const int32_t* who = start + b + 1;
+      for (int i = 0; i < n; ++i)
+        if (idx[i] < 0 || idx[i] >= b)
+          return nmx_fail(NMX_ERR_INVALID, "op %d (%s): index %d at element %d outside its source of length %d", k, nm,
+                          idx[i], i, b);
+      if (start[0] != 0 || start[b] != n)
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): transposed index does not cover %d elements", k, nm, n);
+      for (int j = 0; j < b; ++j) {
+        if (start[j + 1] < start[j] || start[j + 1] > n)
+          return nmx_fail(NMX_ERR_INVALID, "op %d (%s): transposed index row %d is not ordered", k, nm, j);
+        for (int t = start[j]; t < start[j + 1]; ++t)
+          if (who[t] < 0 || who[t] >= n || idx[who[t]] != j)
+            return nmx_fail(NMX_ERR_INVALID, "op %d (%s): transposed index entry %d does not match the index", k, nm, t);
+      }
+    } else {  // NMX_OP_MATVEC
+      if (aux <= 0 || !slot_ok(a, aux))
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): vector slot %d of length %d out of range", k, nm, a, aux);
+      if (!const_ok(b, 2 * (int64_t)n * aux))
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): matrix constant %d (%d x %d and its transpose) outside the pool "
+                        "of %d", k, nm, b < 0 ? ~b : b, n, aux, p.num_consts);
+    }
+    def_len[dst] = (int32_t)dst_len;
+    cursor += dst_len;
+    if (k == p.num_ops - 1 && dst_len != 1)
+      return nmx_fail(NMX_ERR_INVALID, "op %d (%s): the last op must define one slot (U), not %d", k, nm, n);
+  }
+  if (cursor != p.num_slots)
+    return nmx_fail(NMX_ERR_INVALID, "program defines %lld slots, num_slots is %d", (long long)cursor, p.num_slots);
+  return NMX_OK;
+}
+
+extern "C" size_t nmx_pe_program_workspace_bytes(int num_slots, int ldc) {
+  if (num_slots <= 0 || ldc <= 0) return 0;
+  return (size_t)ldc * 2 * (size_t)num_slots * sizeof(float);
+}
+
+extern "C" int nmx_pe_program(const nmx_program* program, const nmx_eval_batch* ev, void* workspace, void* stream) {
+  if (!ev || !ev->z || !ev->grad || !ev->pe) return nmx_fail(NMX_ERR_INVALID, "eval batch has NULL pointers");
+  if (ev->num_chains <= 0 || ev->ldc < ev->num_chains)
+    return nmx_fail(NMX_ERR_INVALID, "bad num_chains/ldc (%d/%d)", ev->num_chains, ev->ldc);
+  if (!program || !program->ops || !program->consts || !workspace || program->num_ops <= 0 || program->dim <= 0 ||
+      program->num_slots <= program->dim || (program->num_index > 0 && !program->index))
+    return nmx_fail(NMX_ERR_INVALID, "bad program or workspace");
+  hipLaunchKernelGGL(k_program, dim3(ev->num_chains), dim3(64), 0, (hipStream_t)stream,
+                     NmxProgram{*program, (float*)workspace}, *ev);
+  return nmx_check_launch("k_program");
+}

@@ -3,10 +3,12 @@ numpyro's API and run through the model front end (numpyro_amd/frontend.py).
 
 They hold their parameters (numbers, arrays, or symbolic values of latent sites while a model
 is traced) and shapes; the arithmetic runs in the fused kernels the front end maps a traced
-model onto, so there is no log_prob here.  Names and signatures follow numpyro:
+model onto, or in the program the front end lowers it to (numpyro_amd/program.py expands each
+log_prob into primitive operations), so there is no log_prob here.  Names and signatures follow numpyro:
 Normal (continuous.py:2171), HalfCauchy (:700), Exponential (:455), Gamma (:490), StudentT
 (:2344), Bernoulli / BernoulliLogits (discrete.py:108-139), GaussianRandomWalk (continuous.py:
-658), MultivariateNormal (:1487); ``.to_event`` / ``.expand`` (distribution.py:377-420).
+658), MultivariateNormal (:1487), HalfNormal (:829), LogNormal (:1166), Cauchy (:217), Poisson
+(discrete.py:748; observed sites only); ``.to_event`` / ``.expand`` (distribution.py:377-420).
 """
 from __future__ import annotations
 
@@ -85,6 +87,50 @@ class HalfCauchy(Distribution):
 
     def params(self):
         return {"scale": self.scale}
+
+
+class HalfNormal(Distribution):
+    support = "positive"
+
+    def __init__(self, scale=1.0):
+        super().__init__(_bshape(scale))
+        self.scale = scale
+
+    def params(self):
+        return {"scale": self.scale}
+
+
+class LogNormal(Distribution):
+    support = "positive"
+
+    def __init__(self, loc=0.0, scale=1.0):
+        super().__init__(_bshape(loc, scale))
+        self.loc, self.scale = loc, scale
+
+    def params(self):
+        return {"loc": self.loc, "scale": self.scale}
+
+
+class Cauchy(Distribution):
+    def __init__(self, loc=0.0, scale=1.0):
+        super().__init__(_bshape(loc, scale))
+        self.loc, self.scale = loc, scale
+
+    def params(self):
+        return {"loc": self.loc, "scale": self.scale}
+
+
+class Poisson(Distribution):
+    """Observed sites only (a discrete latent cannot be sampled by HMC)."""
+
+    support = "nonnegative_integer"
+
+    def __init__(self, rate):
+        super().__init__(_bshape(rate))
+        self.rate = rate
+
+    def params(self):
+        return {"rate": self.rate}
 
 
 class Exponential(Distribution):

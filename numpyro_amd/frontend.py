@@ -10,8 +10,13 @@ observed data; a matcher per supported structure checks the priors' constants an
 likelihood's expression and returns the bound fused potential, with the model's own site
 names.  Supported structures: the reference's examples on the hot path (covtype logistic
 regression, eight schools, funnel and its LocScaleReparam(0) form, stochastic volatility,
-the BNN) and the test targets (diagonal normal, multivariate normal).  Anything else raises
-NotImplementedError naming the traced sites: there is no generic (autodiff) path.
+the BNN) and the test targets (diagonal normal, multivariate normal).  For anything else
+potential_from_model raises NotImplementedError naming the traced sites; NUTS / HMC then hand
+the model to the program compiler (numpyro_amd/program.py compile_model), which lowers the
+traced log-joint to a straight-line program of primitive operations evaluated, with its
+reverse-mode adjoint, by one HIP kernel (csrc/potential_program.hip).  A model that matches a
+fused kernel always gets it; a model outside the program compiler's class (rank-2 latents,
+bounded supports, reparam configs, operations outside numpyro_amd.jnp) is refused by both.
 """
 from __future__ import annotations
 
@@ -312,7 +317,9 @@ def potential_from_model(model, args=(), kwargs=None):
 
 
 # ----------------------------------------------------------------------------- deterministic sites
-_SYM_UNARY = {"tanh": "tanh", "exp": "exp", "sqrt": "sqrt", "log": "log", "neg": "neg"}
+_SYM_UNARY = {"tanh": "tanh", "exp": "exp", "sqrt": "sqrt", "log": "log", "neg": "neg", "log1p": "log1p",
+              "square": "square"}
+_SYM_OTHER = ("matmul", "sum", "getitem")
 _SYM_BINARY = {"add": "add", "sub": "sub", "mul": "mul", "div": "div", "pow": "pow"}
 
 
@@ -332,7 +339,22 @@ def eval_sym(x, values):
         return getattr(torch, _SYM_UNARY[x.op])(eval_sym(x.args[0], values))
     if x.op in _SYM_BINARY:
         a, b = (eval_sym(v, values) for v in x.args)
+        # a batch of scalars against a batch of vectors: the scalar's event dimension is added
+        ra, rb = len(shape_of(x.args[0])), len(shape_of(x.args[1]))
+        if ra < rb and torch.is_tensor(a) and a.dim() > ra:
+            a = a.reshape(*a.shape, *([1] * (rb - ra)))
+        if rb < ra and torch.is_tensor(b) and b.dim() > rb:
+            b = b.reshape(*b.shape, *([1] * (ra - rb)))
         return getattr(torch, _SYM_BINARY[x.op])(a, b)
+    if x.op == "sum":  # full reduction of a vector (the event dimension)
+        v = eval_sym(x.args[0], values)
+        return v.sum(-1) if len(shape_of(x.args[0])) else v
+    if x.op == "getitem":  # leading event axis of a vector: the last dimension of the batch of draws
+        v, idx = eval_sym(x.args[0], values), x.args[1]
+        if not isinstance(idx, (int, slice)):
+            idx = torch.as_tensor(_host(idx), dtype=torch.long, device=v.device)
+        axis = v.dim() - len(shape_of(x.args[0]))
+        return v[(slice(None),) * axis + (idx,)]
     if x.op == "matmul":
         a_s, b_s = x.args
         a, b = eval_sym(a_s, values), eval_sym(b_s, values)
@@ -354,10 +376,10 @@ def _check_sym(x, name):
     """Raise NotImplementedError at model-mapping time for an expression eval_sym cannot evaluate."""
     if not isinstance(x, Sym) or x.op == "latent":
         return
-    if x.op not in _SYM_UNARY and x.op not in _SYM_BINARY and x.op != "matmul":
+    if x.op not in _SYM_UNARY and x.op not in _SYM_BINARY and x.op not in _SYM_OTHER:
         raise NotImplementedError(f"deterministic site {name!r}: operation {x.op!r} is not supported "
-                                  f"(supported: {sorted(_SYM_UNARY) + sorted(_SYM_BINARY) + ['matmul']})")
-    for a in x.args:
+                                  f"(supported: {sorted(_SYM_UNARY) + sorted(_SYM_BINARY) + list(_SYM_OTHER)})")
+    for a in x.args[:1] if x.op == "getitem" else x.args:
         _check_sym(a, name)
 
 

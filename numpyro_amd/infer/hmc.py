@@ -330,10 +330,20 @@ class HMC(MCMCKernel):
             self._potential = self._model.potential(*model_args, **(model_kwargs or {}))
         elif self._model is not None:
             # model front end: trace the model and map it onto its fused kernel
-            # (initialize_model, numpyro/infer/util.py:632-800)
+            # (initialize_model, numpyro/infer/util.py:632-800); a structure without one is
+            # lowered to a program for the generic HIP kernel (numpyro_amd/program.py)
             from ..frontend import potential_from_model
+            from ..program import compile_model
 
-            self._potential = potential_from_model(self._model, model_args, model_kwargs)
+            try:
+                self._potential = potential_from_model(self._model, model_args, model_kwargs)
+            except NotImplementedError as fused:
+                if not str(fused).startswith("no fused kernel"):
+                    raise
+                try:
+                    self._potential = compile_model(self._model, model_args, model_kwargs)
+                except NotImplementedError as generic:
+                    raise NotImplementedError(f"{fused}; {generic}") from None
         return self._potential
 
     def init_radius(self):

@@ -1,5 +1,5 @@
 """The array functions the reference's example models call on jax.numpy (matmul, dot, tanh,
-exp, sqrt, zeros, ones, shape), working on NumPy / torch arrays and on the symbolic values of
+exp, log, log1p, sqrt, square, sum, zeros, ones, shape; indexing a vector), working on NumPy / torch arrays and on the symbolic values of
 latent sites while the model front end traces a model (numpyro_amd/frontend.py).  Write
 ``from numpyro_amd import jnp`` where a numpyro model has ``import jax.numpy as jnp``."""
 from __future__ import annotations
@@ -35,6 +35,29 @@ class Sym:
     def __rmatmul__(self, o): return matmul(o, self)
     def __pow__(self, o): return self._bin("pow", o)
 
+    __iter__ = None  # indexable, not iterable (NumPy must not unpack a Sym element by element)
+
+    def __getitem__(self, idx):
+        """Indexing on the leading axis with an int, a slice or a constant integer array
+        (``alpha[group]``): Sym("getitem", (x, idx))."""
+        if not self.shape:
+            raise IndexError("a scalar symbolic value cannot be indexed")
+        n = self.shape[0]
+        if isinstance(idx, Sym) or isinstance(idx, tuple):
+            raise NotImplementedError("symbolic values are indexed on the leading axis by an int, a slice or a "
+                                      "constant integer array")
+        if isinstance(idx, slice):
+            lead = (len(range(*idx.indices(n))),)
+        else:
+            arr = np.asarray(idx.cpu().numpy() if hasattr(idx, "cpu") else idx)
+            if arr.dtype == bool or not np.issubdtype(arr.dtype, np.integer):
+                raise NotImplementedError("symbolic values are indexed by integers (no boolean masks)")
+            if arr.size and (arr.min() < -n or arr.max() >= n):
+                raise IndexError(f"index out of range for a symbolic value of length {n}")
+            idx = int(arr) if arr.ndim == 0 else arr
+            lead = arr.shape
+        return Sym("getitem", (self, idx), lead + self.shape[1:])
+
     def __repr__(self):
         if self.op == "latent":
             return f"<{self.args[0]}>"
@@ -62,6 +85,17 @@ tanh = _unary("tanh", np.tanh)
 exp = _unary("exp", np.exp)
 sqrt = _unary("sqrt", np.sqrt)
 log = _unary("log", np.log)
+log1p = _unary("log1p", np.log1p)
+square = _unary("square", np.square)
+
+
+def sum(x, axis=None):  # noqa: A001  (jax.numpy's name)
+    """Full reduction of a value of rank <= 1."""
+    if isinstance(x, Sym):
+        if len(x.shape) > 1 or axis not in (None, 0, -1):
+            raise NotImplementedError("jnp.sum of a symbolic value is the full reduction of a vector")
+        return Sym("sum", (x,), ())
+    return np.sum(np.asarray(x) if not hasattr(x, "cpu") else x.cpu().numpy(), axis=axis)
 
 
 def matmul(a, b):

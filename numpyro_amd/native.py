@@ -106,9 +106,25 @@ class EvalBatch(ctypes.Structure):
                 ("num_chains", ctypes.c_int32), ("ldc", ctypes.c_int32)]
 
 
+# enum nmx_opcode (order matters): unary, binary, then the ops that read across elements
+OPCODES = ["neg", "exp", "log", "sqrt", "tanh", "log1p", "square", "softplus", "lgamma",
+           "add", "sub", "mul", "div", "pow", "reduce_sum", "gather", "matvec"]
+OPCODE = {n: i for i, n in enumerate(OPCODES)}
+OP_WORDS = 8  # NMX_OP_WORDS: opcode, dst, a, b, n, sa, sb, aux
+
+
+class Program(ctypes.Structure):
+    """Mirror of nmx_program."""
+
+    _fields_ = [("ops", c_vp), ("consts", c_vp), ("index", c_vp),
+                ("num_ops", ctypes.c_int32), ("num_slots", ctypes.c_int32), ("num_consts", ctypes.c_int32),
+                ("num_index", ctypes.c_int32), ("dim", ctypes.c_int32)]
+
+
 _P = ctypes.POINTER
 _cfgp = _P(NutsConfig)
 _evp = _P(EvalBatch)
+_progp = _P(Program)
 
 # name -> (restype, argtypes); kept in sync with include/numpyro_amd.h (tests check it).
 SIGNATURES: dict[str, tuple] = {
@@ -149,6 +165,9 @@ SIGNATURES: dict[str, tuple] = {
     "nmx_pe_bnn": (c_int, [c_vp, c_vp, c_int, c_int, c_int, _evp, c_vp, c_vp]),
     "nmx_pe_bnn_workspace_bytes": (c_size, [c_int, c_int, c_int]),
     "nmx_pe_bnn_rows": (c_int, [c_vp, c_vp, c_int, c_int, c_int, _evp, c_vp, c_vp, c_vp]),
+    "nmx_program_check": (c_int, [_progp]),
+    "nmx_pe_program_workspace_bytes": (c_size, [c_int, c_int]),
+    "nmx_pe_program": (c_int, [_progp, _evp, c_vp, c_vp]),
     "nmx_logreg_packed_bytes": (c_size, [c_i64, c_int]),
     "nmx_logreg_pack": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     "nmx_logreg_workspace_bytes": (c_size, [c_i64, c_int, c_int]),

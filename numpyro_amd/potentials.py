@@ -78,7 +78,7 @@ class Potential:
         out, o = {}, 0
         for name, shape, _ in self.sites:
             n = int(np.prod(shape, dtype=np.int64))
-            out[name] = flat[..., o:o + n].reshape(*flat.shape[:-1], *shape)
+            out[name] = flat[..., o:o + n].reshape(tuple(flat.shape[:-1]) + tuple(shape))
             o += n
         return out
 

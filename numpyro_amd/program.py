@@ -1,0 +1,654 @@
+"""Program compiler: the generic device path of the model front end.
+
+The reference turns any model into ``potential_fn`` by running its effect handlers
+(numpyro/infer/util.py:546-611 potential_fn_gen / get_potential_fn) and differentiates it with
+JAX.  Here ``compile_model`` traces the model once (frontend.trace_model), expands every site's
+``log_prob`` into primitive operations and lowers U(z) = -log p(z) - log|J|(z) to a
+straight-line *program* over f32 vectors (include/numpyro_amd.h "program potential"): a flat
+int32 op array, a constant pool and an index pool.  One HIP kernel (csrc/potential_program.hip)
+evaluates the program and its reverse-mode adjoint for every evaluated chain in one launch,
+behind the ``Potential.evaluate`` contract, so dense mass, HMC / NUTS, sharding, diagnostics
+and deterministic sites work as for the fused kernels.
+
+The kernel knows nothing about distributions: a new distribution is a ``_LOGPROB`` entry here.
+Host passes: subexpressions without a latent are folded in float64 into the constant pool
+(every normalising constant ends there), common subexpressions are shared (a ``Sym`` used twice
+is one value), ``log(exp(x))`` is ``x``.  ``Program.run_host`` is a float64 NumPy interpreter
+of the same program, forward and reverse: it defines the kernel's semantics op by op.
+
+Model class: latent sites of rank 0 or 1 with support ``real`` or ``positive`` (the kernel
+sees u = log x and the program adds -sum(u), as NmxEightSchools does) from Normal, StudentT,
+Cauchy, HalfCauchy, HalfNormal, LogNormal, Exponential, Gamma; observed sites from those plus
+BernoulliLogits / BernoulliProbs / Poisson; parameters that are constants or expressions of
+latents over numpyro_amd.jnp's operations.  Anything else raises NotImplementedError naming
+the site.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import numpy as np
+
+from . import distributions as dist
+from . import native
+from .frontend import _base, _host, _with_traced_deterministics, trace_model
+from .jnp import Sym
+from .native import OPCODE
+from .potentials import POSITIVE, REAL, Potential
+
+_UNARY = ("neg", "exp", "log", "sqrt", "tanh", "log1p", "square", "softplus", "lgamma")
+_BINARY = ("add", "sub", "mul", "div", "pow")
+
+
+def _lgamma64(x):
+    import torch
+
+    return torch.lgamma(torch.as_tensor(np.asarray(x, np.float64))).numpy()
+
+
+def _digamma64(x):
+    import torch
+
+    return torch.special.digamma(torch.as_tensor(np.asarray(x, np.float64))).numpy()
+
+
+_HOST_FWD = {
+    "neg": lambda x: -x, "exp": np.exp, "log": np.log, "sqrt": np.sqrt, "tanh": np.tanh, "log1p": np.log1p,
+    "square": np.square, "softplus": lambda x: np.maximum(x, 0.0) + np.log1p(np.exp(-np.abs(x))),
+    "lgamma": _lgamma64,
+    "add": np.add, "sub": np.subtract, "mul": np.multiply, "div": np.divide, "pow": np.power,
+}
+
+
+def _host_rev(op, gd, x, y, out):
+    """(adjoint of a, adjoint of b) of one elementwise op, as the kernel's NmxProgram::rev."""
+    if op == "neg":
+        return -gd, None
+    if op == "exp":
+        return gd * out, None
+    if op == "log":
+        return gd / x, None
+    if op == "sqrt":
+        return gd * 0.5 / out, None
+    if op == "tanh":
+        return gd * (1.0 - out * out), None
+    if op == "log1p":
+        return gd / (1.0 + x), None
+    if op == "square":
+        return gd * (2.0 * x), None
+    if op == "softplus":
+        return gd / (1.0 + np.exp(-x)), None
+    if op == "lgamma":
+        return gd * _digamma64(x), None
+    if op == "add":
+        return gd, gd
+    if op == "sub":
+        return gd, -gd
+    if op == "mul":
+        return gd * y, gd * x
+    if op == "div":
+        return gd / y, -(gd * out) / y
+    return gd * (y * np.power(x, y - 1.0)), gd * (out * np.log(x))  # pow
+
+
+class Program:
+    """A lowered model: ``ops`` int32 [num_ops, 8] = (opcode, dst, a, b, n, sa, sb, aux),
+    ``consts`` (float64 here, float32 on the device), ``index`` int32; slots [0, dim) are z."""
+
+    def __init__(self, ops, consts, index, num_slots, dim):
+        self.ops = np.ascontiguousarray(np.asarray(ops, np.int32).reshape(-1, native.OP_WORDS))
+        self.consts64 = np.ascontiguousarray(np.asarray(consts, np.float64).reshape(-1))
+        if self.consts64.size == 0:
+            self.consts64 = np.zeros(1)
+        with np.errstate(over="ignore"):
+            self.consts = np.ascontiguousarray(self.consts64.astype(np.float32))
+        self.index = np.ascontiguousarray(np.asarray(index, np.int32).reshape(-1))
+        self.num_slots, self.dim = int(num_slots), int(dim)
+
+    @property
+    def num_ops(self):
+        return self.ops.shape[0]
+
+    def native_struct(self, ops=None, consts=None, index=None):
+        """nmx_program over the given arrays' pointers (default: this program's host arrays)."""
+        def p(a):
+            return None if a is None or a.size == 0 else int(a.ctypes.data)
+
+        ops = self.ops if ops is None else ops
+        consts = self.consts if consts is None else consts
+        index = self.index if index is None else index
+        return native.Program(ops=p(ops), consts=p(consts), index=p(index), num_ops=ops.shape[0],
+                              num_slots=self.num_slots, num_consts=consts.size, num_index=index.size, dim=self.dim)
+
+    def native_check(self):
+        """(status, message) of nmx_program_check on the host arrays: needs no GPU."""
+        lib = native.lib()
+        st = lib.nmx_program_check(ctypes.byref(self.native_struct()))
+        return st, (lib.nmx_last_error().decode(errors="replace") if st else "")
+
+    def describe(self):
+        names = native.OPCODES
+        return [f"{k}: {names[o[0]]} dst={o[1]} a={o[2]} b={o[3]} n={o[4]} sa={o[5]} sb={o[6]} aux={o[7]}"
+                for k, o in enumerate(self.ops.tolist())]
+
+    # ------------------------------------------------------------------ float64 interpreter
+    def run_host(self, Z):
+        """(U [C], dU/dz [C, D]) of the rows of Z [C, D], in float64: the program forward and
+        reverse, op by op as the kernel runs it (only the order inside sums differs)."""
+        Z = np.atleast_2d(np.asarray(Z, np.float64))
+        C, S, D = Z.shape[0], self.num_slots, self.dim
+        assert Z.shape[1] == D
+        cp, ix, names = self.consts64, self.index, native.OPCODES
+        v = np.zeros((C, S))
+        g = np.zeros((C, S))
+        v[:, :D] = Z
+
+        def operand(ref, n, stride):
+            ln = n if stride else 1
+            return v[:, ref:ref + ln] if ref >= 0 else cp[None, ~ref:~ref + ln]
+
+        ops = self.ops.tolist()
+        with np.errstate(all="ignore"):
+            for op, dst, a, b, n, sa, sb, aux in ops:
+                nm = names[op]
+                if nm in _UNARY:
+                    v[:, dst:dst + n] = _HOST_FWD[nm](operand(a, n, sa))
+                elif nm in _BINARY:
+                    v[:, dst:dst + n] = _HOST_FWD[nm](operand(a, n, sa), operand(b, n, sb))
+                elif nm == "reduce_sum":
+                    v[:, dst] = v[:, a:a + n].sum(1)
+                elif nm == "gather":
+                    v[:, dst:dst + n] = v[:, a + ix[aux:aux + n]]
+                else:  # matvec
+                    M = cp[~b:~b + n * aux].reshape(n, aux)
+                    v[:, dst:dst + n] = v[:, a:a + aux] @ M.T
+            g[:, S - 1] = 1.0
+            for op, dst, a, b, n, sa, sb, aux in reversed(ops):
+                nm = names[op]
+                gd = g[:, dst:dst + (1 if nm == "reduce_sum" else n)]
+                if nm in _UNARY or nm in _BINARY:
+                    x = operand(a, n, sa)
+                    y = operand(b, n, sb) if nm in _BINARY else None
+                    da, db = _host_rev(nm, gd, x, y, v[:, dst:dst + n])
+                    for ref, stride, d in ((a, sa, da), (b, sb, db)):
+                        if d is None or ref < 0:
+                            continue
+                        d = np.broadcast_to(d, (C, n))
+                        if stride:
+                            g[:, ref:ref + n] += d
+                        else:
+                            g[:, ref] += d.sum(1)
+                elif nm == "reduce_sum":
+                    g[:, a:a + n] += gd
+                elif nm == "gather":
+                    np.add.at(g, (slice(None), a + ix[aux:aux + n]), gd)
+                else:
+                    M = cp[~b:~b + n * aux].reshape(n, aux)
+                    g[:, a:a + aux] += gd @ M
+        return v[:, S - 1].copy(), g[:, :D].copy()
+
+    # ------------------------------------------------------------------ cost model
+    def flops_per_eval(self, num_chains=1):
+        """Arithmetic operations of one evaluation, forward + reverse (a transcendental counts 1)."""
+        f = 0.0
+        for op, dst, a, b, n, sa, sb, aux in self.ops.tolist():
+            nm = native.OPCODES[op]
+            f += 4.0 * n * aux if nm == "matvec" else 2.0 * n if nm in ("reduce_sum", "gather") else 4.0 * n
+        return f * num_chains
+
+    def bytes_per_eval(self):
+        """Bytes one chain evaluation moves through its tape (values and adjoints, f32): the
+        adjoints' zero fill, each op's operand reads and result write forward, and backward the
+        result's adjoint, the operands and the read-modify-write of the operands' adjoints.
+        Constants and indices are shared by all chains and stay cached."""
+        el = self.num_slots + 2 * self.dim  # zero fill, z in, grad out
+        for op, dst, a, b, n, sa, sb, aux in self.ops.tolist():
+            nm = native.OPCODES[op]
+            if nm == "matvec":
+                src = [aux]
+            elif nm == "gather":
+                src = [n]
+            elif nm == "reduce_sum":
+                src = [n]
+            else:
+                src = [(n if s else 1) for r, s in ((a, sa), (b, sb) if nm in _BINARY else (-1, 0)) if r >= 0]
+            nd = 1 if nm == "reduce_sum" else n
+            el += sum(src) + nd  # forward
+            el += nd + sum(src) + nd + 2 * sum(src)  # reverse: adjoint in, operands, result, adjoints +=
+        return 4 * el
+
+
+# ------------------------------------------------------------------------------------------
+# Builder: values, folding, sharing
+# ------------------------------------------------------------------------------------------
+class _V:
+    """Compile-time value of n elements: a float64 constant (``c``) or program slots (``slot``)."""
+
+    __slots__ = ("b", "n", "c", "slot")
+
+    def __init__(self, b, n, c=None, slot=None):
+        self.b, self.n, self.c, self.slot = b, int(n), c, slot
+
+    @property
+    def is_const(self):
+        return self.c is not None
+
+    def __add__(self, o): return self.b.ew("add", self, o)
+    def __radd__(self, o): return self.b.ew("add", o, self)
+    def __sub__(self, o): return self.b.ew("sub", self, o)
+    def __rsub__(self, o): return self.b.ew("sub", o, self)
+    def __mul__(self, o): return self.b.ew("mul", self, o)
+    def __rmul__(self, o): return self.b.ew("mul", o, self)
+    def __truediv__(self, o): return self.b.ew("div", self, o)
+    def __rtruediv__(self, o): return self.b.ew("div", o, self)
+    def __pow__(self, o): return self.b.ew("pow", self, o)
+    def __neg__(self): return self.b.ew("neg", self)
+
+
+class _Builder:
+    def __init__(self, dim):
+        self.dim = dim
+        self.ops, self.consts, self.index = [], [], []
+        self.n_consts = 0
+        self.next_slot = dim
+        self.memo = {}  # (op, operand keys) -> value: common subexpressions
+        self.pool = {}  # constant bytes -> pool offset
+        self.made_by = {}  # slot -> (op name, operand value) for the log(exp(x)) rewrite
+
+    def const(self, x):
+        if isinstance(x, _V):
+            return x
+        a = np.asarray(x, np.float64)
+        if a.ndim > 1:
+            raise NotImplementedError("a constant of rank > 1 is only supported as the matrix of a matmul")
+        return _V(self, max(a.size, 1), c=a.reshape(-1).copy())
+
+    def _pool(self, arr):
+        arr = np.asarray(arr, np.float64).reshape(-1)
+        key = arr.tobytes()
+        if key not in self.pool:
+            self.pool[key] = self.n_consts
+            self.consts.append(arr)
+            self.n_consts += arr.size
+        return self.pool[key]
+
+    def _ref(self, v):
+        return v.slot if not v.is_const else ~self._pool(v.c)
+
+    def _emit(self, name, n_dst, a, b, n, sa, sb, aux, key):
+        if key in self.memo:
+            return self.memo[key]
+        dst = self.next_slot
+        self.next_slot += n_dst
+        self.ops.append([OPCODE[name], dst, a, b, n, sa, sb, aux])
+        out = _V(self, n_dst, slot=dst)
+        self.memo[key] = out
+        return out
+
+    def ew(self, name, a, b=None):
+        a = self.const(a)
+        b = None if b is None else self.const(b)
+        if a.is_const and (b is None or b.is_const):
+            with np.errstate(all="ignore"):
+                return self.const(_HOST_FWD[name](a.c) if b is None else _HOST_FWD[name](a.c, b.c))
+        n = a.n if b is None else max(a.n, b.n)
+        for v in (a, b):
+            if v is not None and v.n not in (1, n):
+                raise NotImplementedError(f"operands of {v.n} and {n} elements do not broadcast")
+        # identities with constants (Normal(0, 1) has loc 0 and scale 1)
+        if b is not None and b.is_const and a.n == n:
+            if (name in ("add", "sub") and np.all(b.c == 0.0)) or (name in ("mul", "div", "pow") and np.all(b.c == 1.0)):
+                return a
+        if b is not None and a.is_const and b.n == n:
+            if (name == "add" and np.all(a.c == 0.0)) or (name == "mul" and np.all(a.c == 1.0)):
+                return b
+        if name == "log" and self.made_by.get(a.slot, ("",))[0] == "exp":
+            return self.made_by[a.slot][1]
+        # x + (-y) is x - y (log densities are written as sums of negated terms); the negation
+        # left without a reader is dropped by program()
+        if name == "add" and not b.is_const and self.made_by.get(b.slot, ("",))[0] == "neg":
+            return self.ew("sub", a, self.made_by[b.slot][1])
+        if name == "add" and not a.is_const and self.made_by.get(a.slot, ("",))[0] == "neg":
+            return self.ew("sub", b, self.made_by[a.slot][1])
+        ra, rb = self._ref(a), (0 if b is None else self._ref(b))
+        sa, sb = int(a.n == n), int(b is not None and b.n == n)
+        out = self._emit(name, n, ra, rb, n, sa, sb, 0, (name, ra, rb, n, sa, sb))
+        self.made_by.setdefault(out.slot, (name, a))
+        return out
+
+    def rsum(self, a):
+        a = self.const(a)
+        if a.is_const:
+            return self.const(a.c.sum())
+        if a.n == 1:
+            return a
+        return self._emit("reduce_sum", 1, a.slot, 0, a.n, 1, 0, 0, ("reduce_sum", a.slot, a.n))
+
+    def gather(self, a, idx):
+        idx = np.asarray(idx, np.int64).reshape(-1)
+        if a.is_const:
+            return self.const(a.c[idx])
+        if idx.size == a.n and np.array_equal(idx, np.arange(a.n)):
+            return a
+        key = ("gather", a.slot, idx.tobytes())
+        if key in self.memo:
+            return self.memo[key]
+        # forward indices, then the transposed (CSR) index of the adjoint's segmented sum
+        who = np.argsort(idx, kind="stable")
+        start = np.concatenate([[0], np.cumsum(np.bincount(idx, minlength=a.n))])
+        aux = len(self.index)
+        self.index += idx.tolist() + start.tolist() + who.tolist()
+        return self._emit("gather", idx.size, a.slot, a.n, idx.size, 1, 0, aux, key)
+
+    def matvec(self, M, a):
+        M = np.asarray(M, np.float64)
+        if a.is_const:
+            return self.const(M @ a.c)
+        off = self._pool(np.concatenate([M.reshape(-1), M.T.reshape(-1)]))
+        return self._emit("matvec", M.shape[0], a.slot, ~off, M.shape[0], 1, 0, M.shape[1], ("matvec", a.slot, off))
+
+    def unary(self, name):
+        return lambda x: self.ew(name, x)
+
+    def program(self):
+        """The ops the last one (U) depends on, renumbered so that each defines the next free slots."""
+        ops, dim = self.ops, self.dim
+        made = {o[1]: k for k, o in enumerate(ops)}
+        binary = range(OPCODE["add"], OPCODE["reduce_sum"])
+
+        def slot_refs(o):
+            return [r for r in ((o[2], o[3]) if o[0] in binary else (o[2],)) if r >= dim]
+
+        live, todo = set(), [len(ops) - 1]
+        while todo:
+            k = todo.pop()
+            if k not in live:
+                live.add(k)
+                todo += [made[r] for r in slot_refs(ops[k])]
+        moved, cursor, out = {}, dim, []
+        for k, o in enumerate(ops):
+            if k not in live:
+                continue
+            o = list(o)
+            for f in ((2, 3) if o[0] in binary else (2,)):
+                if o[f] >= dim:
+                    o[f] = moved[o[f]]
+            moved[o[1]] = cursor
+            o[1] = cursor
+            cursor += 1 if o[0] == OPCODE["reduce_sum"] else o[4]
+            out.append(o)
+        consts = np.concatenate(self.consts) if self.consts else np.zeros(0)
+        return Program(out, consts, self.index, cursor, dim)
+
+
+# ------------------------------------------------------------------------------------------
+# log_prob expansions (numpyro/distributions/continuous.py, discrete.py): each returns the
+# terms of the elementwise log density, kept apart so that scalar and constant terms are not
+# broadcast to the site's size.
+# ------------------------------------------------------------------------------------------
+_LOG_PI = math.log(math.pi)
+_HALF_LOG_2PI = 0.5 * math.log(2 * math.pi)
+
+
+def _lp_normal(B, d, x, logx):
+    z = (x - d["loc"]) / d["scale"]
+    return [-0.5 * B.ew("square", z), -B.ew("log", d["scale"]), B.const(-_HALF_LOG_2PI)]
+
+
+def _lp_student_t(B, d, x, logx):
+    df, y = d["df"], (x - d["loc"]) / d["scale"]
+    return [B.ew("lgamma", (df + 1.0) * 0.5) - B.ew("lgamma", df * 0.5), -0.5 * B.ew("log", df),
+            B.const(-0.5 * _LOG_PI), -B.ew("log", d["scale"]),
+            -0.5 * (df + 1.0) * B.ew("log1p", B.ew("square", y) / df)]
+
+
+def _lp_cauchy(B, d, x, logx):
+    return [B.const(-_LOG_PI), -B.ew("log", d["scale"]), -B.ew("log1p", B.ew("square", (x - d["loc"]) / d["scale"]))]
+
+
+def _lp_half_cauchy(B, d, x, logx):
+    return [B.const(math.log(2.0) - _LOG_PI), -B.ew("log", d["scale"]),
+            -B.ew("log1p", B.ew("square", x / d["scale"]))]
+
+
+def _lp_half_normal(B, d, x, logx):
+    return [-0.5 * B.ew("square", x / d["scale"]), -B.ew("log", d["scale"]), B.const(0.5 * math.log(2.0 / math.pi))]
+
+
+def _lp_log_normal(B, d, x, logx):
+    return [-0.5 * B.ew("square", (logx - d["loc"]) / d["scale"]), -B.ew("log", d["scale"]),
+            B.const(-_HALF_LOG_2PI), -logx]
+
+
+def _lp_exponential(B, d, x, logx):
+    return [B.ew("log", d["rate"]), -(d["rate"] * x)]
+
+
+def _lp_gamma(B, d, x, logx):
+    c = d["concentration"]
+    return [c * B.ew("log", d["rate"]), -B.ew("lgamma", c), (c - 1.0) * logx, -(d["rate"] * x)]
+
+
+def _lp_bernoulli_logits(B, d, x, logx):
+    return [x * d["logits"], -B.ew("softplus", d["logits"])]
+
+
+def _lp_bernoulli_probs(B, d, x, logx):
+    return [x * B.ew("log", d["probs"]), (1.0 - x) * B.ew("log1p", -d["probs"])]
+
+
+def _lp_poisson(B, d, x, logx):
+    return [x * B.ew("log", d["rate"]), -d["rate"], -B.ew("lgamma", x + 1.0)]
+
+
+# distribution -> (expansion, parameter names, may be latent)
+_LOGPROB = {
+    dist.Normal: (_lp_normal, ("loc", "scale"), True),
+    dist.StudentT: (_lp_student_t, ("df", "loc", "scale"), True),
+    dist.Cauchy: (_lp_cauchy, ("loc", "scale"), True),
+    dist.HalfCauchy: (_lp_half_cauchy, ("scale",), True),
+    dist.HalfNormal: (_lp_half_normal, ("scale",), True),
+    dist.LogNormal: (_lp_log_normal, ("loc", "scale"), True),
+    dist.Exponential: (_lp_exponential, ("rate",), True),
+    dist.Gamma: (_lp_gamma, ("concentration", "rate"), True),
+    dist.BernoulliLogits: (_lp_bernoulli_logits, ("logits",), False),
+    dist.BernoulliProbs: (_lp_bernoulli_probs, ("probs",), False),
+    dist.Poisson: (_lp_poisson, ("rate",), False),
+}
+
+
+class _Refuse(NotImplementedError):
+    pass
+
+
+def _refuse(site, why):
+    raise _Refuse(f"program compiler: site {site!r}: {why}")
+
+
+class _Lowering:
+    """Sym expressions -> builder values, one value per Sym object."""
+
+    def __init__(self, B, latents):
+        self.B, self.latents = B, latents  # latents: name -> constrained value
+        self.seen = {}  # id(Sym) -> (Sym, value)
+
+    def __call__(self, x, site):
+        if not isinstance(x, Sym):
+            a = np.asarray(_host(x), np.float64)
+            if a.ndim > 1:
+                _refuse(site, f"a constant of shape {a.shape} (rank > 1) outside a matmul")
+            return self.B.const(a)
+        hit = self.seen.get(id(x))
+        if hit is not None:
+            return hit[1]
+        if len(x.shape) > 1:
+            _refuse(site, f"expression {x!r} of shape {x.shape}: values of rank > 1 are not supported")
+        out = self._lower(x, site)
+        self.seen[id(x)] = (x, out)
+        return out
+
+    def _lower(self, x, site):
+        B, op = self.B, x.op
+        if op == "latent":
+            if x.args[0] not in self.latents:
+                _refuse(site, f"unknown latent {x.args[0]!r}")
+            return self.latents[x.args[0]]
+        if op in ("neg", "exp", "log", "sqrt", "tanh", "log1p", "square"):
+            return B.ew(op, self(x.args[0], site))
+        if op in _BINARY:
+            return B.ew(op, self(x.args[0], site), self(x.args[1], site))
+        if op == "sum":
+            return B.rsum(self(x.args[0], site))
+        if op == "getitem":
+            src, idx = self(x.args[0], site), x.args[1]
+            sel = np.arange(src.n)[idx] if isinstance(idx, (int, slice)) else np.asarray(_host(idx))
+            if np.ndim(sel) > 1:
+                _refuse(site, "indexing with an index array of rank > 1")
+            sel = np.asarray(sel, np.int64).reshape(-1)
+            return B.gather(src, np.where(sel < 0, sel + src.n, sel))
+        if op == "matmul":
+            a, b = x.args
+            if isinstance(a, Sym) == isinstance(b, Sym):
+                _refuse(site, "matmul of two symbolic values (supported: a constant matrix with a symbolic vector)")
+            if isinstance(b, Sym):  # M @ v
+                M, vec = np.asarray(_host(a), np.float64), self(b, site)
+                M = M.reshape(1, -1) if M.ndim == 1 else M
+            else:  # v @ M
+                M, vec = np.asarray(_host(b), np.float64), self(a, site)
+                M = M.reshape(1, -1) if M.ndim == 1 else M.T
+            if M.ndim != 2 or M.shape[1] != vec.n or len(x.shape) > 1:
+                _refuse(site, f"matmul of shapes {np.shape(_host(a)) if not isinstance(a, Sym) else a.shape} and "
+                              f"{np.shape(_host(b)) if not isinstance(b, Sym) else b.shape}")
+            return B.matvec(M, vec)
+        _refuse(site, f"operation {op!r} is not supported (supported: {sorted(_UNARY[:7] + _BINARY)}, sum, "
+                      "getitem, matmul)")
+
+
+def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
+    """Trace ``model(*args, **kwargs)`` and lower its potential to a ProgramPotential."""
+    cfg = getattr(model, "_nmx_reparam", None)
+    fn = getattr(model, "_nmx_model", model)
+    trace = trace_model(fn, args, kwargs, cfg)
+    for name in trace.reparam:
+        _refuse(name, "reparam configs are not supported")
+    lat = sorted((s for s in trace.sites.values() if s.obs is None), key=lambda s: s.name)
+    if not lat:
+        raise _Refuse("program compiler: the model has no latent sample sites")
+    sites, offsets, o = [], {}, 0
+    for s in lat:
+        base = _base(s.fn)
+        if len(s.shape) > 1:
+            _refuse(s.name, f"latent of shape {s.shape}: latents of rank > 1 are not supported")
+        entry = _LOGPROB.get(type(base))
+        if entry is None or not entry[2]:
+            _refuse(s.name, f"{type(base).__name__} is not supported as a latent site")
+        if base.support not in ("real", "positive"):
+            _refuse(s.name, f"support {base.support!r} is not supported (real and positive are)")
+        n = int(np.prod(s.shape, dtype=np.int64))
+        if n <= 0:
+            _refuse(s.name, "empty site")
+        sites.append((s.name, tuple(s.shape), POSITIVE if base.support == "positive" else REAL))
+        offsets[s.name] = (o, n)
+        o += n
+    B = _Builder(o)
+    unconstrained = {name: _V(B, n, slot=off) for name, (off, n) in offsets.items()}
+    constrained = {name: (B.ew("exp", unconstrained[name]) if tr == POSITIVE else unconstrained[name])
+                   for name, _, tr in sites}
+    lower = _Lowering(B, constrained)
+
+    const_total = 0.0
+    scalars = []  # scalar terms of log p + log|J|
+    for s in trace.sites.values():
+        base = _base(s.fn)
+        entry = _LOGPROB.get(type(base))
+        if entry is None:
+            _refuse(s.name, f"{type(base).__name__} is not supported")
+        expand, pnames, _ = entry
+        try:
+            d = {p: lower(getattr(base, p), s.name) for p in pnames}
+            if s.obs is None:
+                x = constrained[s.name]
+                logx = unconstrained[s.name] if base.support == "positive" else None
+                n_site = offsets[s.name][1]
+            else:
+                xv = np.asarray(_host(s.obs), np.float64)
+                if xv.ndim > 1:
+                    _refuse(s.name, f"observations of shape {xv.shape}: rank > 1 is not supported")
+                x = B.const(xv)
+                with np.errstate(all="ignore"):
+                    logx = B.const(np.log(x.c)) if base.support == "positive" else None
+                n_site = max(int(np.prod(s.shape, dtype=np.int64)), x.n)
+            terms = expand(B, d, x, logx)
+            if s.obs is None and base.support == "positive":
+                terms.append(unconstrained[s.name])  # ExpTransform log|J| = u
+        except _Refuse:
+            raise
+        except NotImplementedError as e:
+            _refuse(s.name, str(e))
+        vec = None
+        for t in terms:
+            t = B.const(t)
+            if t.n not in (1, n_site):
+                _refuse(s.name, f"a log-density term of {t.n} elements at a site of {n_site}")
+            if t.is_const:
+                const_total += float(t.c.sum()) if t.n == n_site else float(t.c[0]) * n_site
+            elif t.n == n_site and n_site > 1:
+                vec = t if vec is None else vec + t
+            else:
+                scalars.append(t * float(n_site) if n_site > 1 else t)
+        if vec is not None:
+            scalars.append(B.rsum(vec))
+    if not scalars:
+        raise _Refuse("program compiler: the log density does not depend on the latent sites")
+    total = scalars[0]
+    for t in scalars[1:]:
+        total = total + t
+    u = B.ew("sub", B.const(-const_total), total)  # U = -log p; always the program's last op
+    assert u.slot == B.next_slot - 1
+    pot = ProgramPotential(B.program(), sites, max_workspace_bytes)
+    return _with_traced_deterministics(pot, trace)
+
+
+class ProgramPotential(Potential):
+    """A traced model's potential as a program (nmx_pe_program): one launch per evaluation."""
+
+    def __init__(self, program, sites, max_workspace_bytes=1 << 30):
+        self.program = program
+        self.sites = list(sites)
+        self.dim = program.dim
+        self.max_workspace_bytes = int(max_workspace_bytes)
+        assert self.dim == sum(int(np.prod(s, dtype=np.int64)) for _, s, _ in self.sites)
+
+    # a single workspace: `slots` stays unset, so the engine keeps the potential on one stream
+
+    def _bind(self, C, ldc, device):
+        import torch
+
+        prog = self.program
+        # a malformed program never reaches the device
+        st, msg = prog.native_check()
+        if st:
+            raise native.NativeError(f"nmx_program_check failed (status {st}): {msg}")
+        wb = native.lib().nmx_pe_program_workspace_bytes(prog.num_slots, ldc)
+        if wb > self.max_workspace_bytes:
+            raise NotImplementedError(
+                f"program potential: the tape of {prog.num_slots} slots for {C} chains (ldc {ldc}) needs a workspace "
+                f"of {wb} bytes, above max_workspace_bytes = {self.max_workspace_bytes}; run fewer chains per engine")
+        self.d_ops = torch.from_numpy(prog.ops).to(device)
+        self.d_consts = torch.from_numpy(prog.consts).to(device)
+        self.d_index = torch.from_numpy(prog.index).to(device) if prog.index.size else None
+        self.workspace = torch.empty(wb, dtype=torch.uint8, device=device)
+        self._cprog = native.Program(ops=native.ptr(self.d_ops), consts=native.ptr(self.d_consts),
+                                     index=native.ptr(self.d_index), num_ops=prog.num_ops, num_slots=prog.num_slots,
+                                     num_consts=prog.consts.size, num_index=prog.index.size, dim=prog.dim)
+
+    def evaluate(self, ev, stream):
+        native.check(native.lib().nmx_pe_program(ctypes.byref(self._cprog), ctypes.byref(ev),
+                                                 native.ptr(self.workspace), stream), "nmx_pe_program")
+
+    def flops_per_eval(self, num_chains):
+        return self.program.flops_per_eval(num_chains)
+
+    def bytes_per_eval(self):
+        return self.program.bytes_per_eval()
