@@ -528,6 +528,63 @@ int nmx_predict_normal(const float* loc, const float* scale, int n, int num_samp
 int nmx_predict_bnn(const float* X, int n, int dx, int dh, int dy, const float* samples, int num_samples,
                     uint64_t seed, float* out, void* stream);
 
+/* ---- predictive programs: Predictive for any traced model of the program compiler's class
+ *      (numpyro_amd/program.py compile_predictive).  The program format above, forward only:
+ *      slots [0, dim) hold the sample's given sites (constrained values, sorted by name; dim may
+ *      be 0: prior predictive), the arithmetic ops are those of enum nmx_opcode, and a *draw* op
+ *      fills its n slots with random variates.  Every distribution is built from the base draws
+ *      below and arithmetic (Normal = loc + scale * draw_normal, ...).  There is no U: the host
+ *      reads each output site as a slice of the sample's tape row.
+ *
+ * A draw op is { opcode, dst, a, 0, n, sa, 0, stream }: a is the parameter (slot or constant,
+ * stride sa in {0, 1}; 0 for the draws without one), n <= 2^24, `stream` the ordinal of the
+ * draw op in the program (0, 1, ...).  Element i of sample s uses the Philox blocks
+ *   w(t) = nmx_rng(seed, s, stream, NMX_EV_PREDICT = 7, i, t),  t = attempt = 0, 1, ...
+ * (counter = (s, stream, 7 << 24 | i, t), s the global sample index), so a draw depends only on
+ * (seed, sample, stream, element).  u01(x) = (x >> 8) 2^-24 in [0, 1), u01_open0(x) =
+ * ((x >> 8) + 1) 2^-24 in (0, 1].  A parameter outside the support gives NaN without a loop;
+ * every loop is bounded by NMX_DRAW_MAX_ATTEMPTS / NMX_POISSON_MAX_STEPS, exhausted -> NaN.
+ *   NMX_DRAW_NORMAL:      sqrt(-2 log u01_open0(w(0).x)) cos(2 pi u01(w(0).y))   (Box-Muller)
+ *   NMX_DRAW_EXPONENTIAL: -log u01_open0(w(0).x)
+ *   NMX_DRAW_CAUCHY:      tan(pi (((w(0).x >> 8) + 0.5) 2^-24 - 0.5))
+ *   NMX_DRAW_BERNOULLI:   u01(w(0).x) < p ? 1 : 0;  NaN unless 0 <= p <= 1
+ *   NMX_DRAW_GAMMA (a = concentration; NaN unless 0 < a < inf): Marsaglia-Tsang with
+ *     a' = a < 1 ? a + 1 : a, d = a' - 1/3, c = 1 / sqrt(9 d); attempt t: x = the Box-Muller
+ *     normal of (w(t).x, w(t).y), v = (1 + c x)^3, accepted when 1 + c x > 0 and
+ *     log u01_open0(w(t).z) < x^2 / 2 + d - d v + d log v; the value is d v, times
+ *     exp(log(u01_open0(w(t).w)) / a) when a < 1.
+ *   NMX_DRAW_POISSON (a = rate; NaN unless 0 <= rate < inf; 0 at rate 0):
+ *     rate < 10: inversion of u = u01(w(0).x): the first k with u <= sum_{j <= k} p_j, p_0 =
+ *       exp(-rate), p_j = p_{j-1} rate / j, or the first k > rate with p_k < 2^-40 (the tail
+ *       left is below the 2^-24 resolution of u), k < NMX_POISSON_MAX_STEPS;
+ *     rate >= 10: Hoermann's PTRS, attempt t with U = u01(w(t).x) - 0.5, V = u01_open0(w(t).y):
+ *       b = 0.931 + 2.53 sqrt(rate), a = -0.059 + 0.02483 b, 1/alpha = 1.1239 + 1.1328 / (b - 3.4),
+ *       v_r = 0.9277 - 3.6224 / (b - 2), us = 0.5 - |U|, k = floor((2 a / us + b) U + rate + 0.43);
+ *       accepted when us >= 0.07 and V <= v_r; rejected when k < 0 or (us < 0.013 and V > us);
+ *       else accepted when log(V / alpha / (a / us^2 + b)) <= -rate + k log rate - lgamma(k + 1).
+ * ---- */
+enum nmx_draw_opcode {
+  NMX_DRAW_NORMAL = 64, NMX_DRAW_EXPONENTIAL, NMX_DRAW_CAUCHY,  /* no parameter */
+  NMX_DRAW_GAMMA, NMX_DRAW_BERNOULLI, NMX_DRAW_POISSON,         /* parameter a */
+  NMX_DRAW_END
+};
+#define NMX_DRAW_MAX_ATTEMPTS 64
+#define NMX_POISSON_MAX_STEPS 96
+#define NMX_POISSON_PTRS_RATE 10.0f
+
+/* Validate a predictive program in HOST memory, as nmx_program_check does, with dim >= 0, draw
+ * ops (parameter, count <= 2^24, stream id = ordinal) and no U; `outputs` is num_outputs x
+ * { slot, n }: each must be a given site inside [0, dim) or lie inside one defined value.
+ * Needs no GPU; names the bad op or output. */
+int nmx_predict_program_check(const nmx_program* host_program, const int32_t* outputs, int num_outputs);
+/* The tape of nmx_predict_program: num_samples rows of num_slots f32. */
+size_t nmx_predict_program_workspace_bytes(int num_slots, int num_samples);
+/* One launch, one wave per sample: row s of `tape` [num_samples][num_slots] is the program run
+ * on row s of `samples` [num_samples][dim] (NULL when dim = 0) with the draws of global sample
+ * index sample_offset + s.  `program` holds DEVICE arrays of a program the check accepted. */
+int nmx_predict_program(const nmx_program* program, const float* samples, int num_samples,
+                        int64_t sample_offset, uint64_t seed, float* tape, void* stream);
+
 /* ---- self tests (no reference counterpart; used by tests and smoke()) ---- */
 /* Philox4x32-10 on device: ctr_key is n x {c0,c1,c2,c3,k0,k1}, out is n x 4 words. */
 int nmx_selftest_philox(const uint32_t* ctr_key, uint32_t* out, int n, void* stream);

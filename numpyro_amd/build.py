@@ -44,7 +44,8 @@ COMMON_FLAGS = [
 #   pair them into v_pk_*_f32, which issue slower beside MFMAs on gfx950; potential_logreg.hip
 #   x3_epi_one);
 # * no floating-point contraction in the step kernels, the small models' potentials and the
-#   program potential (a per-chain body in a header, nmx_program.h, like the small models): the
+#   program potential and predictive program (bodies in a header, nmx_program.h, like the small
+#   models; the predictive draws' accept tests round like their NumPy restatement): the
 #   same device function is inlined into several kernels (the launched step, the persistent
 #   schedule, the sync / async schedules), and whether the backend fuses a * b + c into an FMA
 #   depends on each kernel's code generation -- with contraction off every kernel rounds every
@@ -52,7 +53,8 @@ COMMON_FLAGS = [
 FILE_FLAGS = {"potential_logreg.hip": ["-fno-slp-vectorize"],
               "nuts.hip": ["-ffp-contract=off"],
               "potential_small.hip": ["-ffp-contract=off"],
-              "potential_program.hip": ["-ffp-contract=off"]}
+              "potential_program.hip": ["-ffp-contract=off"],
+              "predictive_program.hip": ["-ffp-contract=off"]}
 
 
 def _headers():

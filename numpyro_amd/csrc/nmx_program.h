@@ -225,3 +225,125 @@ struct NmxProgram {
     if (lane == 0) ev.pe[c] = v[S - 1];
   }
 };
+
+// ---- predictive programs (include/numpyro_amd.h "predictive programs"): the forward half of
+// the interpreter plus draw ops, one wave per posterior sample.  Element i of a draw is produced
+// by lane i % 64 from its own Philox blocks nmx_rng(seed, sample, stream, NMX_EV_PREDICT, i,
+// attempt): no cross-lane traffic, no atomics.  Word assignment (the header states it in full,
+// program.py PredictiveProgram.run_host is its float64 restatement):
+//   normal       Box-Muller cos branch of (w0.x, w0.y)        exponential  -log u01_open0(w0.x)
+//   cauchy       tan(pi (mid24(w0.x) - 0.5))                  bernoulli    u01(w0.x) < p
+//   gamma        attempt t: normal of (wt.x, wt.y), accept uniform wt.z, boost uniform wt.w
+//   poisson      rate < 10: inversion of u01(w0.x); else PTRS, attempt t: (wt.x, wt.y)
+// Every loop has a compile-time bound (NMX_DRAW_MAX_ATTEMPTS, NMX_POISSON_MAX_STEPS) and a
+// parameter outside the support returns NaN before any loop: bad input cannot make a lane spin.
+__device__ __forceinline__ float nmx_draw_normal(const nmx_u4& w) {
+  float z, unused;
+  nmx_box_muller(w.x, w.y, z, unused);
+  return z;
+}
+
+__device__ __forceinline__ float nmx_draw_gamma(float a, uint64_t seed, uint32_t s, uint32_t stream, uint32_t i) {
+  if (!(a > 0.0f) || a == INFINITY) return NAN;
+  const bool boost = a < 1.0f;
+  const float a1 = boost ? a + 1.0f : a;
+  const float d = a1 - 1.0f / 3.0f, c = 1.0f / sqrtf(9.0f * d);
+  for (uint32_t t = 0; t < NMX_DRAW_MAX_ATTEMPTS; ++t) {
+    const nmx_u4 w = nmx_rng(seed, s, stream, NMX_EV_PREDICT, i, t);
+    const float x = nmx_draw_normal(w);
+    const float y = 1.0f + c * x;
+    if (!(y > 0.0f)) continue;
+    const float v = y * y * y;
+    if (logf(nmx_u01_open0(w.z)) < 0.5f * x * x + d - d * v + d * logf(v))
+      return boost ? d * v * expf(logf(nmx_u01_open0(w.w)) / a) : d * v;
+  }
+  return NAN;
+}
+
+__device__ __forceinline__ float nmx_draw_poisson(float rate, uint64_t seed, uint32_t s, uint32_t stream,
+                                                  uint32_t i) {
+  if (!(rate >= 0.0f) || rate == INFINITY) return NAN;
+  if (rate == 0.0f) return 0.0f;
+  if (rate < NMX_POISSON_PTRS_RATE) {
+    const float u = nmx_u01(nmx_rng(seed, s, stream, NMX_EV_PREDICT, i, 0).x);
+    float p = expf(-rate), sum = p, k = 0.0f;
+    for (int step = 0; step < NMX_POISSON_MAX_STEPS; ++step) {
+      if (u <= sum) return k;
+      k += 1.0f;
+      p = p * rate / k;
+      sum += p;
+      if (p < 0x1p-40f && k > rate) return k;
+    }
+    return NAN;
+  }
+  const float log_rate = logf(rate), b = 0.931f + 2.53f * sqrtf(rate), a = -0.059f + 0.02483f * b;
+  const float inv_alpha = 1.1239f + 1.1328f / (b - 3.4f), v_r = 0.9277f - 3.6224f / (b - 2.0f);
+  for (uint32_t t = 0; t < NMX_DRAW_MAX_ATTEMPTS; ++t) {
+    const nmx_u4 w = nmx_rng(seed, s, stream, NMX_EV_PREDICT, i, t);
+    const float U = nmx_u01(w.x) - 0.5f, V = nmx_u01_open0(w.y);
+    const float us = 0.5f - fabsf(U);
+    const float k = floorf((2.0f * a / us + b) * U + rate + 0.43f);
+    if (us >= 0.07f && V <= v_r) return k;
+    if (!(k >= 0.0f) || (us < 0.013f && V > us)) continue;
+    if (logf(V * inv_alpha / (a / (us * us) + b)) <= -rate + k * log_rate - lgammaf(k + 1.0f)) return k;
+  }
+  return NAN;
+}
+
+struct NmxPredict {
+  NmxProgram prog;  // p.dim = given coordinates; ws unused (the tape holds values only)
+  uint64_t seed;
+
+  __device__ __forceinline__ static bool is_draw(const NmxOp& o) { return o.op >= NMX_DRAW_NORMAL; }
+  __device__ __forceinline__ static bool has_param(const NmxOp& o) { return o.op >= NMX_DRAW_GAMMA; }
+  // the barrier rule of NmxProgram::reads_scalar_slot for a draw's parameter
+  __device__ __forceinline__ static bool reads_scalar_slot(const NmxOp& o) {
+    return has_param(o) && o.a >= 0 && !o.sa && o.n != 1;
+  }
+
+  __device__ __forceinline__ void draw(const NmxOp& o, float* v, int lane, uint32_t s) const {
+    const uint32_t stream = (uint32_t)o.aux;
+    for (int i = lane; i < o.n; i += 64) {
+      const float a = has_param(o) ? prog.operand(v, o.a, i * o.sa) : 0.0f;
+      float r;
+      switch (o.op) {
+        case NMX_DRAW_NORMAL: r = nmx_draw_normal(nmx_rng(seed, s, stream, NMX_EV_PREDICT, i, 0)); break;
+        case NMX_DRAW_EXPONENTIAL:
+          r = -logf(nmx_u01_open0(nmx_rng(seed, s, stream, NMX_EV_PREDICT, i, 0).x));
+          break;
+        case NMX_DRAW_CAUCHY: {
+          const uint32_t x = nmx_rng(seed, s, stream, NMX_EV_PREDICT, i, 0).x;
+          r = tanf(3.14159265358979323846f * (((float)(x >> 8) + 0.5f) * 5.9604644775390625e-08f - 0.5f));
+          break;
+        }
+        case NMX_DRAW_GAMMA: r = nmx_draw_gamma(a, seed, s, stream, i); break;
+        case NMX_DRAW_BERNOULLI:
+          r = (a >= 0.0f && a <= 1.0f) ? (nmx_u01(nmx_rng(seed, s, stream, NMX_EV_PREDICT, i, 0).x) < a ? 1.0f : 0.0f)
+                                       : NAN;
+          break;
+        default: r = nmx_draw_poisson(a, seed, s, stream, i); break;  // NMX_DRAW_POISSON
+      }
+      NMX_DCHECK(o.dst >= prog.p.dim && o.dst + i < prog.p.num_slots);
+      v[o.dst + i] = r;
+    }
+  }
+
+  // row `row` of samples / tape, global sample index s; called by all 64 lanes of a one-wave workgroup
+  __device__ __forceinline__ void operator()(const float* samples, float* tape, int row, uint32_t s, int lane) const {
+    const nmx_program& p = prog.p;
+    float* v = tape + (size_t)row * p.num_slots;
+    NMX_DCHECK(row >= 0 && p.dim >= 0 && p.dim <= p.num_slots && (p.dim == 0 || samples));
+    for (int d = lane; d < p.dim; d += 64) v[d] = samples[(size_t)row * p.dim + d];
+    __syncthreads();
+    for (int k = 0; k < p.num_ops; ++k) {
+      const NmxOp o = prog.load(k);
+      if (is_draw(o)) {
+        if (reads_scalar_slot(o)) __syncthreads();
+        draw(o, v, lane, s);
+      } else {
+        if (NmxProgram::crosses(o) || NmxProgram::reads_scalar_slot(o)) __syncthreads();
+        prog.forward(o, v, lane);
+      }
+    }
+  }
+};

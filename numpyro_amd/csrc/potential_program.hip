@@ -22,24 +22,31 @@ __global__ __launch_bounds__(64) void k_program(NmxProgram prog, nmx_eval_batch 
 const char* const OP_NAMES[NMX_NUM_OPCODES] = {"neg", "exp", "log", "sqrt", "tanh", "log1p", "square", "softplus",
                                                "lgamma", "add", "sub", "mul", "div", "pow", "reduce_sum",
                                                "gather", "matvec"};
+const char* const DRAW_NAMES[NMX_DRAW_END - NMX_DRAW_NORMAL] = {"draw_normal", "draw_exponential", "draw_cauchy",
+                                                                "draw_gamma", "draw_bernoulli", "draw_poisson"};
 
 }  // namespace
 
-extern "C" int nmx_program_check(const nmx_program* hp) {
+// The check of both program kinds.  A potential program (predictive = false) has dim > 0, the
+// arithmetic ops alone and U as its last slot; a predictive program may have dim = 0 and draw
+// ops, has no U, and its outputs { slot, n } must lie in z or inside one defined value.
+int nmx_program_check_impl(const nmx_program* hp, bool predictive, const int32_t* outputs, int num_outputs) {
   if (!hp || !hp->ops || !hp->consts) return nmx_fail(NMX_ERR_INVALID, "program has NULL arrays");
   const nmx_program& p = *hp;
-  if (p.num_ops <= 0 || p.dim <= 0 || p.num_slots <= p.dim || p.num_consts < 0 || p.num_index < 0)
+  if (p.num_ops <= 0 || p.dim < (predictive ? 0 : 1) || p.num_slots <= p.dim || p.num_consts < 0 || p.num_index < 0)
     return nmx_fail(NMX_ERR_INVALID, "program sizes: %d ops, %d slots, dim %d, %d constants, %d indices", p.num_ops,
                     p.num_slots, p.dim, p.num_consts, p.num_index);
   if (p.num_index > 0 && !p.index) return nmx_fail(NMX_ERR_INVALID, "program has a NULL index pool");
   // length of the value defined at each slot (0: not the start of a value)
   std::vector<int32_t> def_len((size_t)p.num_slots, 0);
   int64_t cursor = p.dim;
+  int num_draws = 0;
   for (int k = 0; k < p.num_ops; ++k) {
     const int32_t* w = p.ops + (size_t)k * NMX_OP_WORDS;
     const int op = w[0], dst = w[1], a = w[2], b = w[3], n = w[4], sa = w[5], sb = w[6], aux = w[7];
-    if (op < 0 || op >= NMX_NUM_OPCODES) return nmx_fail(NMX_ERR_INVALID, "op %d: bad opcode %d", k, op);
-    const char* nm = OP_NAMES[op];
+    const bool draw = predictive && op >= NMX_DRAW_NORMAL && op < NMX_DRAW_END;
+    if (!draw && (op < 0 || op >= NMX_NUM_OPCODES)) return nmx_fail(NMX_ERR_INVALID, "op %d: bad opcode %d", k, op);
+    const char* nm = draw ? DRAW_NAMES[op - NMX_DRAW_NORMAL] : OP_NAMES[op];
     if (n <= 0) return nmx_fail(NMX_ERR_INVALID, "op %d (%s): count %d <= 0", k, nm, n);
     const int64_t dst_len = op == NMX_OP_REDUCE_SUM ? 1 : n;
     if (dst != cursor || cursor + dst_len > p.num_slots)
@@ -52,7 +59,20 @@ extern "C" int nmx_program_check(const nmx_program* hp) {
       return def_len[ref] >= len;
     };
     auto const_ok = [&](int ref, int64_t len) { return ref < 0 && (int64_t)~ref + len <= p.num_consts; };
-    if (op < NMX_OP_REDUCE_SUM) {
+    if (draw) {
+      if (n > 0x01000000)
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): count %d above 2^24 (the counter's element field)", k, nm, n);
+      if (aux != num_draws)
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): stream id %d is not the draw's ordinal %d", k, nm, aux, num_draws);
+      ++num_draws;
+      if (op >= NMX_DRAW_GAMMA) {
+        if (sa != 0 && sa != 1) return nmx_fail(NMX_ERR_INVALID, "op %d (%s): stride %d not 0 or 1", k, nm, sa);
+        const int64_t la = sa ? n : 1;
+        if (a >= 0 ? !slot_ok(a, la) : !const_ok(a, la))
+          return nmx_fail(NMX_ERR_INVALID, "op %d (%s): parameter %s %d (x%lld) out of range", k, nm,
+                          a >= 0 ? "slot" : "constant", a >= 0 ? a : ~a, (long long)la);
+      }
+    } else if (op < NMX_OP_REDUCE_SUM) {
       const bool binary = op >= NMX_OP_ADD;
       if ((sa != 0 && sa != 1) || (sb != 0 && sb != 1))
         return nmx_fail(NMX_ERR_INVALID, "op %d (%s): strides %d, %d not 0 or 1", k, nm, sa, sb);
@@ -99,13 +119,30 @@ extern "C" int nmx_program_check(const nmx_program* hp) {
     }
     def_len[dst] = (int32_t)dst_len;
     cursor += dst_len;
-    if (k == p.num_ops - 1 && dst_len != 1)
+    if (!predictive && k == p.num_ops - 1 && dst_len != 1)
       return nmx_fail(NMX_ERR_INVALID, "op %d (%s): the last op must define one slot (U), not %d", k, nm, n);
   }
   if (cursor != p.num_slots)
     return nmx_fail(NMX_ERR_INVALID, "program defines %lld slots, num_slots is %d", (long long)cursor, p.num_slots);
+  if (num_outputs < 0 || (num_outputs > 0 && !outputs)) return nmx_fail(NMX_ERR_INVALID, "bad output list");
+  for (int j = 0; j < num_outputs; ++j) {
+    const int64_t slot = outputs[2 * j], n = outputs[2 * j + 1];
+    bool ok = n > 0 && slot >= 0 && slot + n <= p.num_slots;
+    if (ok && slot < p.dim) ok = slot + n <= p.dim;
+    // inside one defined value: walk back to the value's first slot
+    if (ok && slot >= p.dim) {
+      int64_t first = slot;
+      while (def_len[first] == 0) --first;  // slot p.dim starts a value (checked above)
+      ok = slot + n <= first + def_len[first];
+    }
+    if (!ok)
+      return nmx_fail(NMX_ERR_INVALID, "output %d: slots [%lld, %lld) are not a given site or inside one defined "
+                      "value (%d slots, dim %d)", j, (long long)slot, (long long)(slot + n), p.num_slots, p.dim);
+  }
   return NMX_OK;
 }
+
+extern "C" int nmx_program_check(const nmx_program* hp) { return nmx_program_check_impl(hp, false, nullptr, 0); }
 
 extern "C" size_t nmx_pe_program_workspace_bytes(int num_slots, int ldc) {
   if (num_slots <= 0 || ldc <= 0) return 0;

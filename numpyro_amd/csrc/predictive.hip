@@ -13,8 +13,6 @@
 
 namespace {
 
-constexpr uint32_t NMX_EV_PREDICT = 7u;
-
 __device__ __forceinline__ nmx_u4 pred_rng(uint64_t seed, int s, int site, int64_t idx, uint32_t sub) {
   return nmx_rng(seed, (uint32_t)s, (uint32_t)site, NMX_EV_PREDICT, (uint32_t)idx, sub);
 }

@@ -1,4 +1,5 @@
-"""``Predictive``: posterior predictive draws for the fused models.
+"""``Predictive``: posterior predictive draws for the fused models, and posterior / prior
+predictive draws for any other traced model of the program compiler's class.
 
 Mirrors ``numpyro.infer.Predictive`` (numpyro/infer/util.py:888-1090): constructed from a
 model and a dict of posterior samples (``MCMC.get_samples()``, leading batch dims per
@@ -17,10 +18,23 @@ reparam.py:140-142) are returned by default, as the reference's ``_predictive`` 
 both the observation and the series length, examples/stochastic_volatility.py:57-65, so -- as in
 the reference -- the observed data come back), funnel and its LocScaleReparam form (no observed
 site: deterministic ``x`` and any ``return_sites``, as examples/funnel.py:84-87 uses it).  Out of
-scope (raise): guides / params (SVI), ``infer_discrete``, prior predictive (no posterior samples).
+scope (raise): guides / params (SVI), ``infer_discrete``, prior predictive of a fused model.
+
+Any other callable model takes the program path: at call time, when the arguments are known, the
+model is traced and lowered to a forward-only program with draw ops
+(numpyro_amd/predictive_program.py compile_predictive) that one HIP kernel runs once per
+posterior sample (csrc/predictive_program.hip).  The sample sites named in ``posterior_samples``
+are the program's inputs; every other site without data is drawn, in the model's order, so a
+drawn site parameterises the later ones.  ``Predictive(model, num_samples=N)`` without posterior
+samples draws every site: prior predictive.  Returned by default: the drawn sites, the observed
+sites whose data was passed (as given) and the deterministic sites; Bernoulli and Poisson sites
+as int32 (an element whose parameter is outside the support, where a float site holds NaN, is
+-1), the others float32.  A model outside the compiler's class raises NotImplementedError
+naming the site.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import warnings
 
@@ -111,11 +125,12 @@ _HOST_ONLY = {"stochastic_volatility", "funnel", "funnel_reparam"}
 
 
 class Predictive:
-    """numpyro.infer.Predictive (numpyro/infer/util.py:888-1090) for the fused models."""
+    """numpyro.infer.Predictive (numpyro/infer/util.py:888-1090) for the fused models and for
+    model functions of the program compiler's class (posterior and prior predictive)."""
 
     def __init__(self, model, posterior_samples=None, *, guide=None, params=None, num_samples=None,
                  return_sites=None, infer_discrete=False, parallel=False, batch_ndims=None,
-                 exclude_deterministic=True):
+                 exclude_deterministic=True, max_workspace_bytes=1 << 30):
         if posterior_samples is None and num_samples is None:
             raise ValueError("Either posterior_samples or num_samples must be specified.")
         if posterior_samples is not None and guide is not None:
@@ -124,12 +139,20 @@ class Predictive:
             raise NotImplementedError("Predictive with a guide / params (SVI) is out of scope here")
         if infer_discrete:
             raise NotImplementedError("infer_discrete is out of scope here")
-        if posterior_samples is None:
-            raise NotImplementedError("prior predictive (no posterior_samples) is out of scope here")
-        if not isinstance(model, P.FusedModel) or model.__name__ not in _PREDICTORS:
+        fused = isinstance(model, P.FusedModel)
+        if posterior_samples is None and (fused or not callable(model)):
+            raise NotImplementedError("prior predictive (no posterior_samples) of a fused model is out of scope here")
+        if not callable(model) or (fused and model.__name__ not in _PREDICTORS):
             raise NotImplementedError(f"no predictive sampler for {model!r} "
-                                      f"(available: {sorted(_PREDICTORS)})")
+                                      f"(available: {sorted(_PREDICTORS)}, or a model function)")
         batch_ndims = 1 if batch_ndims is None else batch_ndims
+        self._fused = fused
+        self.max_workspace_bytes = int(max_workspace_bytes)
+        if posterior_samples is None:  # prior predictive: every site is drawn
+            if int(num_samples) <= 0:
+                raise ValueError(f"num_samples must be positive, got {num_samples}")
+            posterior_samples = {}
+            batch_ndims = 1
         batch_shape = None
         proto = None
         for name, v in posterior_samples.items():
@@ -139,8 +162,10 @@ class Predictive:
                                  f"but got {shp} and {batch_shape}")
             if batch_shape is None:
                 batch_shape, proto = shp, name
-        if batch_shape is None:
+        if batch_shape is None and (fused or num_samples is None):
             raise ValueError("No sample sites in posterior samples to infer `num_samples`.")
+        if batch_shape is None:
+            batch_shape = (int(num_samples),)
         batch_size = int(math.prod(batch_shape))
         if num_samples is not None and num_samples != batch_size:
             warnings.warn(f"Sample's batch dimension size {batch_size} is different from the provided "
@@ -157,6 +182,8 @@ class Predictive:
         self.parallel = parallel
 
     def __call__(self, rng_key, *args, **kwargs):
+        if not self._fused:
+            return self._call_program(rng_key, args, kwargs)
         observed, sampler = _PREDICTORS[self.model.__name__]
         nb = self.batch_ndims
         S = self.num_samples
@@ -190,3 +217,77 @@ class Predictive:
                 continue
             out[n] = v.reshape(*self._batch_shape, *v.shape[1:])
         return out
+
+    # ------------------------------------------------------------------ program path
+    def _call_program(self, rng_key, args, kwargs):
+        from ..frontend import eval_sym
+        from ..jnp import Sym, shape_of
+        from ..predictive_program import compile_predictive
+
+        nb, S = self.batch_ndims, self.num_samples
+        flat = {k: torch.as_tensor(v).reshape(S, *v.shape[nb:]) for k, v in self.posterior_samples.items()}
+        prog = compile_predictive(self.model, args, kwargs, given=flat)
+        for name, _, n, shape in prog.inputs:
+            if tuple(flat[name].shape[1:]) != tuple(shape):
+                raise ValueError(f"posterior samples of site {name!r} have shape {tuple(flat[name].shape[1:])} per "
+                                 f"draw, the model's site has {tuple(shape)}")
+        if torch.cuda.is_available():
+            device = torch.device("cuda", torch.cuda.current_device())
+        elif prog.num_ops:
+            raise RuntimeError("Predictive needs a GPU (the program runs on a HIP kernel)")
+        else:
+            device = torch.device("cpu")  # nothing is drawn: observed data / given sites
+        given = {name: flat[name].to(device, torch.float32) for name, _, _, _ in prog.inputs}
+        draws = self._run_program(prog, given, key_to_seed(rng_key), device) if prog.num_ops else {}
+        for name, (value, integer) in prog.observed.items():
+            draws[name] = _observed(value, S, device, torch.int32 if integer else torch.float32)
+        dets = {o.name: draws.pop(o.name) for o in prog.outputs if not o.streams}
+        for name, expr in prog.host_deterministics.items():
+            if not self.exclude_deterministic and name in flat:
+                dets[name] = flat[name].to(device)
+                continue
+            ev = tuple(shape_of(expr)) if isinstance(expr, Sym) else tuple(np.shape(expr))
+            v = eval_sym(expr, given) if isinstance(expr, Sym) else torch.as_tensor(np.asarray(expr, np.float32))
+            dets[name] = v.to(device).expand(S, *ev).clone() if tuple(v.shape) != (S,) + ev else v
+        names = list(draws) + list(dets) if self.return_sites is None else list(self.return_sites)
+        out = {}
+        for n in names:
+            v = draws[n] if n in draws else dets[n] if n in dets else flat[n].to(device) if n in flat else None
+            if v is not None:
+                out[n] = v.reshape(*self._batch_shape, *v.shape[1:])
+        return out
+
+    def _run_program(self, prog, given, seed, device):
+        """{output site: [S, *shape]} of the program over all samples, in chunks whose tape stays
+        under max_workspace_bytes; a draw depends on the global sample index, not on the chunk."""
+        st, msg = prog.native_check()  # a malformed program never reaches the device
+        if st:
+            raise native.NativeError(f"nmx_predict_program_check failed (status {st}): {msg}")
+        S = self.num_samples
+        x = (torch.cat([given[name].reshape(S, n) for name, _, n, _ in prog.inputs], 1).contiguous()
+             if prog.inputs else None)
+        row_bytes = lib().nmx_predict_program_workspace_bytes(prog.num_slots, 1)
+        chunk = min(S, self.max_workspace_bytes // row_bytes)
+        if chunk <= 0:
+            raise NotImplementedError(f"predictive program: one sample's tape of {prog.num_slots} slots needs "
+                                      f"{row_bytes} bytes, above max_workspace_bytes = {self.max_workspace_bytes}")
+        d_ops = torch.from_numpy(prog.ops).to(device)
+        d_consts = torch.from_numpy(prog.consts).to(device)
+        d_index = torch.from_numpy(prog.index).to(device) if prog.index.size else None
+        cprog = native.Program(ops=ptr(d_ops), consts=ptr(d_consts), index=ptr(d_index), num_ops=prog.num_ops,
+                               num_slots=prog.num_slots, num_consts=prog.consts.size, num_index=prog.index.size,
+                               dim=prog.dim)
+        tape = torch.empty(chunk, prog.num_slots, dtype=torch.float32, device=device)
+        parts = {o.name: [] for o in prog.outputs}
+        for s0 in range(0, S, chunk):
+            m = min(chunk, S - s0)
+            check(lib().nmx_predict_program(ctypes.byref(cprog), ptr(x[s0:]) if x is not None else None, m, s0, seed,
+                                            ptr(tape), native.stream_ptr()), "nmx_predict_program")
+            for o in prog.outputs:
+                v = tape[:m, o.slot:o.slot + o.n]  # a view of the tape: copied out before the next chunk
+                if o.integer:  # whole numbers, or NaN where the parameter is outside the support: -1
+                    v = torch.nan_to_num(v, nan=-1.0).to(torch.int32)
+                else:
+                    v = v.clone()
+                parts[o.name].append(v.reshape(m, *o.shape))
+        return {k: v[0] if len(v) == 1 else torch.cat(v) for k, v in parts.items()}

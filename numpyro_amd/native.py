@@ -113,6 +113,16 @@ OPCODE = {n: i for i, n in enumerate(OPCODES)}
 OP_WORDS = 8  # NMX_OP_WORDS: opcode, dst, a, b, n, sa, sb, aux
 
 
+# enum nmx_draw_opcode: the draw ops of a predictive program, apart from the arithmetic opcodes
+DRAW_BASE = 64
+DRAW_OPCODES = ["draw_normal", "draw_exponential", "draw_cauchy", "draw_gamma", "draw_bernoulli", "draw_poisson"]
+DRAW_OPCODE = {n: DRAW_BASE + i for i, n in enumerate(DRAW_OPCODES)}
+DRAW_MAX_ATTEMPTS = 64  # NMX_DRAW_MAX_ATTEMPTS
+POISSON_MAX_STEPS = 96  # NMX_POISSON_MAX_STEPS
+POISSON_PTRS_RATE = 10.0  # NMX_POISSON_PTRS_RATE
+DRAW_MAX_ELEMENTS = 1 << 24  # the counter's element field
+
+
 class Program(ctypes.Structure):
     """Mirror of nmx_program."""
 
@@ -168,6 +178,9 @@ SIGNATURES: dict[str, tuple] = {
     "nmx_program_check": (c_int, [_progp]),
     "nmx_pe_program_workspace_bytes": (c_size, [c_int, c_int]),
     "nmx_pe_program": (c_int, [_progp, _evp, c_vp, c_vp]),
+    "nmx_predict_program_check": (c_int, [_progp, c_vp, c_int]),
+    "nmx_predict_program_workspace_bytes": (c_size, [c_int, c_int]),
+    "nmx_predict_program": (c_int, [_progp, c_vp, c_int, c_i64, c_u64, c_vp, c_vp]),
     "nmx_logreg_packed_bytes": (c_size, [c_i64, c_int]),
     "nmx_logreg_pack": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     "nmx_logreg_workspace_bytes": (c_size, [c_i64, c_int, c_int]),

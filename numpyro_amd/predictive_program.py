@@ -1,0 +1,412 @@
+"""Predictive programs: posterior and prior predictive draws for the generic path of the model
+front end.
+
+The reference's ``Predictive`` re-runs the model once per posterior sample with the given sites
+substituted and every other site sampled (numpyro/infer/util.py:803-885 _predictive, :888-1090).
+``compile_predictive`` traces the model once (frontend.trace_model) and lowers that forward run
+to a straight-line program of the program compiler's format (numpyro_amd/program.py, the same
+builder: folding, sharing and refusals are the same) in which a site that is neither observed
+nor given is *drawn*: a draw op fills its slots with base variates (standard normal, exponential,
+Cauchy; gamma(concentration), Bernoulli(probs), Poisson(rate)) and the existing arithmetic ops
+build the distribution from them (``_DRAW``).  A drawn site's value then parameterises the later
+sites, so prior predictive of a hierarchical model runs ``mu -> theta -> obs`` in one program.
+One HIP kernel (csrc/predictive_program.hip) runs the program once per posterior sample.
+
+Randomness is the device's Philox stream for predictive draws: element i of sample s of the draw
+op with stream id k (its ordinal in the program) uses the blocks ``words(s, k, i, attempt)``; a
+draw depends only on (seed, sample, stream, element).  ``PredictiveProgram.run_host`` is a NumPy
+interpreter of the same program that defines every draw op word by word (float64; float32 runs
+the same arithmetic in float32, the calibration of the device tests).
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import numpy as np
+
+from . import distributions as dist
+from . import native
+from .frontend import _base, _host, trace_model
+from .jnp import Sym, shape_of
+from .program import _BINARY, _HOST_FWD, _LOGPROB, _UNARY, Program, _Builder, _Lowering, _Refuse, _refuse, _V
+
+_DRAW_NAME = {v: k for k, v in native.DRAW_OPCODE.items()}
+_U24 = 5.9604644775390625e-08  # 2^-24
+
+
+# ------------------------------------------------------------------------------------------
+# samplers (numpyro/distributions/continuous.py, discrete.py `sample`): base draws + arithmetic
+# ------------------------------------------------------------------------------------------
+def _dr_normal(B, d, n):
+    return d["loc"] + d["scale"] * B.draw("draw_normal", n)
+
+
+def _dr_student_t(B, d, n):
+    # z sqrt(df / chi2(df)), chi2(df) = 2 gamma(df / 2)
+    z = B.draw("draw_normal", n)
+    g = B.draw("draw_gamma", n, d["df"] * 0.5)
+    return d["loc"] + d["scale"] * (z * B.ew("sqrt", d["df"] / (2.0 * g)))
+
+
+def _dr_cauchy(B, d, n):
+    return d["loc"] + d["scale"] * B.draw("draw_cauchy", n)
+
+
+def _dr_half_cauchy(B, d, n):
+    return B.ew("sqrt", B.ew("square", d["scale"] * B.draw("draw_cauchy", n)))
+
+
+def _dr_half_normal(B, d, n):
+    return B.ew("sqrt", B.ew("square", d["scale"] * B.draw("draw_normal", n)))
+
+
+def _dr_log_normal(B, d, n):
+    return B.ew("exp", d["loc"] + d["scale"] * B.draw("draw_normal", n))
+
+
+def _dr_exponential(B, d, n):
+    return B.draw("draw_exponential", n) / d["rate"]
+
+
+def _dr_gamma(B, d, n):
+    return B.draw("draw_gamma", n, d["concentration"]) / d["rate"]
+
+
+def _dr_bernoulli_logits(B, d, n):
+    return B.draw("draw_bernoulli", n, 1.0 / (1.0 + B.ew("exp", -d["logits"])))
+
+
+def _dr_bernoulli_probs(B, d, n):
+    return B.draw("draw_bernoulli", n, d["probs"])
+
+
+def _dr_poisson(B, d, n):
+    return B.draw("draw_poisson", n, d["rate"])
+
+
+_DRAW = {
+    dist.Normal: _dr_normal, dist.StudentT: _dr_student_t, dist.Cauchy: _dr_cauchy,
+    dist.HalfCauchy: _dr_half_cauchy, dist.HalfNormal: _dr_half_normal, dist.LogNormal: _dr_log_normal,
+    dist.Exponential: _dr_exponential, dist.Gamma: _dr_gamma, dist.BernoulliLogits: _dr_bernoulli_logits,
+    dist.BernoulliProbs: _dr_bernoulli_probs, dist.Poisson: _dr_poisson,
+}
+assert set(_DRAW) == set(_LOGPROB)
+_INTEGER = (dist.BernoulliLogits, dist.BernoulliProbs, dist.Poisson)
+
+
+class Output:
+    """A site the program computes: ``n`` tape slots from ``slot``, of the site's ``shape``;
+    ``streams`` are the stream ids of the site's own draw ops."""
+
+    def __init__(self, name, slot, n, shape, integer, streams=()):
+        self.name, self.slot, self.n, self.shape = name, int(slot), int(n), tuple(shape)
+        self.integer, self.streams = bool(integer), tuple(streams)
+
+    def __iter__(self):  # (name, slot, n, shape, integer?)
+        return iter((self.name, self.slot, self.n, self.shape, self.integer))
+
+    def __repr__(self):
+        return f"{self.name}: slots [{self.slot}, {self.slot + self.n}) shape {self.shape}" + \
+            (" int" if self.integer else "")
+
+
+def _sym_latents(x, out):
+    if isinstance(x, Sym):
+        if x.op == "latent":
+            out.add(x.args[0])
+        else:
+            for a in (x.args[:1] if x.op == "getitem" else x.args):
+                _sym_latents(a, out)
+    return out
+
+
+class PredictiveProgram(Program):
+    """A forward-only program: slots [0, dim) hold the given sites (``inputs``: (name, offset,
+    n, shape) in sorted name order, constrained values), ``outputs`` the drawn sites and the
+    deterministic sites that depend on one; ``observed`` the sites that keep their data (name ->
+    (data, integer?)) and
+    ``host_deterministics`` the deterministic expressions of given sites alone."""
+
+    def __init__(self, ops, consts, index, num_slots, dim, inputs, outputs, observed, host_deterministics):
+        super().__init__(ops, consts, index, num_slots, dim)
+        self.inputs, self.outputs = list(inputs), list(outputs)
+        self.observed, self.host_deterministics = dict(observed), dict(host_deterministics)
+
+    @property
+    def num_draws(self):
+        return int((self.ops[:, 0] >= native.DRAW_BASE).sum())
+
+    def output_table(self):
+        return np.ascontiguousarray(np.asarray([[o.slot, o.n] for o in self.outputs], np.int32).reshape(-1, 2))
+
+    def native_check(self, outputs=None):
+        """(status, message) of nmx_predict_program_check on the host arrays: needs no GPU."""
+        lib = native.lib()
+        table = self.output_table() if outputs is None else np.ascontiguousarray(np.asarray(outputs, np.int32))
+        st = lib.nmx_predict_program_check(ctypes.byref(self.native_struct()),
+                                           int(table.ctypes.data) if table.size else None, table.shape[0])
+        return st, (lib.nmx_last_error().decode(errors="replace") if st else "")
+
+    def op_names(self):
+        return [_DRAW_NAME[o] if o >= native.DRAW_BASE else native.OPCODES[o] for o in self.ops[:, 0].tolist()]
+
+    def describe(self):
+        return [f"{k}: {nm} dst={o[1]} a={o[2]} b={o[3]} n={o[4]} sa={o[5]} sb={o[6]} aux={o[7]}"
+                for k, (nm, o) in enumerate(zip(self.op_names(), self.ops.tolist()))]
+
+    def flatten_inputs(self, samples, dtype=np.float64):
+        """[S, dim] from a dict name -> [S, *site shape] (or an array [S, dim], or S when dim = 0)."""
+        if isinstance(samples, (int, np.integer)):
+            assert self.dim == 0, "a sample count alone needs a program without given sites"
+            return np.zeros((int(samples), 0), dtype)
+        if isinstance(samples, dict):
+            S = len(next(iter(samples.values())))
+            cols = [np.asarray(samples[name], dtype).reshape(S, n) for name, _, n, _ in self.inputs]
+            return np.concatenate(cols, 1) if cols else np.zeros((S, 0), dtype)
+        return np.atleast_2d(np.asarray(samples, dtype))
+
+    # ------------------------------------------------------------------ NumPy interpreter
+    def run_host(self, samples, seed, words, dtype=np.float64, sample_offset=0, info=None):
+        """The program on every row of ``samples`` (see flatten_inputs) in ``dtype`` arithmetic:
+        {output site: [S, *shape]} as ``dtype`` arrays (an integer site holds whole numbers, or NaN
+        where the draw is undefined).  ``words(seed, sample, stream, element, attempt)`` ->
+        [..., 4] uint32 are the Philox blocks of nmx_rng(seed, sample, stream, NMX_EV_PREDICT,
+        element, attempt) over broadcasting index arrays (this module does not generate them: the
+        tests pass the oracle's Philox).  ``info``, a dict, receives {stream id: accepted attempt
+        [S, n]} of every draw op (-1: none).  The draw ops are defined here word by word; the
+        kernel's header (csrc/nmx_program.h, include/numpyro_amd.h) states the same assignment."""
+        T = np.dtype(dtype).type
+        Z = self.flatten_inputs(samples, dtype)
+        S, NS, D = Z.shape[0], self.num_slots, self.dim
+        assert Z.shape[1] == D
+        cp = self.consts64.astype(dtype) if T is np.float64 else self.consts.astype(dtype)
+        ix = self.index
+        v = np.zeros((S, NS), dtype)
+        v[:, :D] = Z
+        rows = (np.arange(S, dtype=np.int64) + int(sample_offset))[:, None]
+
+        def operand(ref, n, stride):
+            ln = n if stride else 1
+            return v[:, ref:ref + ln] if ref >= 0 else cp[None, ~ref:~ref + ln]
+
+        def blocks(stream, n, attempt):
+            return np.asarray(words(seed, rows, stream, np.arange(n, dtype=np.int64)[None, :], attempt), np.uint32)
+
+        fwd = dict(_HOST_FWD, lgamma=lambda x: _lgamma(x, dtype))
+        with np.errstate(all="ignore"):
+            for (op, dst, a, b, n, sa, sb, aux), nm in zip(self.ops.tolist(), self.op_names()):
+                if nm in _UNARY:
+                    v[:, dst:dst + n] = fwd[nm](operand(a, n, sa))
+                elif nm in _BINARY:
+                    v[:, dst:dst + n] = fwd[nm](operand(a, n, sa), operand(b, n, sb))
+                elif nm == "reduce_sum":
+                    v[:, dst] = v[:, a:a + n].sum(1)
+                elif nm == "gather":
+                    v[:, dst:dst + n] = v[:, a + ix[aux:aux + n]]
+                elif nm == "matvec":
+                    M = cp[~b:~b + n * aux].reshape(n, aux)
+                    v[:, dst:dst + n] = v[:, a:a + aux] @ M.T
+                else:
+                    par = None if nm in ("draw_normal", "draw_exponential", "draw_cauchy") else \
+                        np.broadcast_to(operand(a, n, sa), (S, n))
+                    out, att = _host_draw(nm, par, lambda t, k=aux, m=n: blocks(k, m, t), (S, n), T)
+                    v[:, dst:dst + n] = out
+                    if info is not None:
+                        info[aux] = att
+        return {o.name: v[:, o.slot:o.slot + o.n].reshape((S,) + o.shape).copy() for o in self.outputs}
+
+
+def _lgamma(x, dtype):
+    import torch
+
+    return torch.lgamma(torch.as_tensor(np.ascontiguousarray(x, dtype))).numpy()
+
+
+def _u01(x, T):
+    return (x >> np.uint32(8)).astype(T) * T(_U24)
+
+
+def _u01_open0(x, T):
+    return ((x >> np.uint32(8)).astype(T) + T(1.0)) * T(_U24)
+
+
+def _box_muller(w, T):
+    rad = np.sqrt(T(-2.0) * np.log(_u01_open0(w[..., 0], T)))
+    return rad * np.cos(T(6.283185307179586) * _u01(w[..., 1], T))
+
+
+def _host_draw(name, par, blocks, shape, T):
+    """(values, accepted attempt) of one draw op over [S, n]; `blocks(t)` are attempt t's words."""
+    nan = T(np.nan)
+    att = np.zeros(shape, np.int32)
+    if name == "draw_normal":
+        return _box_muller(blocks(0), T), att
+    if name == "draw_exponential":
+        return -np.log(_u01_open0(blocks(0)[..., 0], T)), att
+    if name == "draw_cauchy":
+        u = ((blocks(0)[..., 0] >> np.uint32(8)).astype(T) + T(0.5)) * T(_U24)
+        return np.tan(T(math.pi) * (u - T(0.5))), att
+    if name == "draw_bernoulli":
+        ok = (par >= 0) & (par <= 1)
+        return np.where(ok, (_u01(blocks(0)[..., 0], T) < par).astype(T), nan), np.where(ok, 0, -1).astype(np.int32)
+    if name == "draw_gamma":
+        return _host_gamma(par, blocks, T)
+    return _host_poisson(par, blocks, T)
+
+
+def _host_gamma(a, blocks, T):
+    """Marsaglia & Tsang (2000), one block per attempt: normal (x, y), accept uniform z, boost w."""
+    ok = (a > 0) & np.isfinite(a)
+    boost = a < 1
+    a1 = np.where(boost, a + T(1.0), a)
+    d = a1 - T(1.0) / T(3.0)
+    c = T(1.0) / np.sqrt(T(9.0) * d)
+    out = np.full(a.shape, np.nan, T)
+    att = np.full(a.shape, -1, np.int32)
+    pending = ok.copy()
+    for t in range(native.DRAW_MAX_ATTEMPTS):
+        if not pending.any():
+            break
+        w = blocks(t)
+        x = _box_muller(w, T)
+        y = T(1.0) + c * x
+        vv = y * y * y
+        acc = pending & (y > 0) & (np.log(_u01_open0(w[..., 2], T)) < T(0.5) * x * x + d - d * vv + d * np.log(vv))
+        g = np.where(boost, d * vv * np.exp(np.log(_u01_open0(w[..., 3], T)) / a), d * vv)
+        out[acc] = g[acc]
+        att[acc] = t
+        pending &= ~acc
+    return out, att
+
+
+def _host_poisson(rate, blocks, T):
+    """rate < 10: inversion of one uniform; else Hoermann's PTRS (1993), one block per attempt."""
+    ok = (rate >= 0) & np.isfinite(rate)
+    out = np.full(rate.shape, np.nan, T)
+    att = np.full(rate.shape, -1, np.int32)
+    zero = ok & (rate == 0)
+    out[zero], att[zero] = 0, 0
+    small = ok & (rate > 0) & (rate < T(native.POISSON_PTRS_RATE))
+    if small.any():
+        u = _u01(blocks(0)[..., 0], T)
+        p = np.exp(-rate)
+        total = p.copy()
+        k = np.zeros(rate.shape, T)
+        pending = small.copy()
+        for _ in range(native.POISSON_MAX_STEPS):
+            done = pending & (u <= total)
+            out[done], att[done] = k[done], 0
+            pending &= ~done
+            if not pending.any():
+                break
+            k = k + T(1.0)
+            p = p * rate / k
+            total = total + p
+            done = pending & (p < T(2.0 ** -40)) & (k > rate)
+            out[done], att[done] = k[done], 0
+            pending &= ~done
+    pending = ok & (rate >= T(native.POISSON_PTRS_RATE))
+    if pending.any():
+        log_rate = np.log(rate)
+        b = T(0.931) + T(2.53) * np.sqrt(rate)
+        a = T(-0.059) + T(0.02483) * b
+        inv_alpha = T(1.1239) + T(1.1328) / (b - T(3.4))
+        v_r = T(0.9277) - T(3.6224) / (b - T(2.0))
+        for t in range(native.DRAW_MAX_ATTEMPTS):
+            if not pending.any():
+                break
+            w = blocks(t)
+            U = _u01(w[..., 0], T) - T(0.5)
+            V = _u01_open0(w[..., 1], T)
+            us = T(0.5) - np.abs(U)
+            k = np.floor((T(2.0) * a / us + b) * U + rate + T(0.43))
+            fast = (us >= T(0.07)) & (V <= v_r)
+            rej = ~(k >= 0) | ((us < T(0.013)) & (V > us))
+            slow = np.log(V * inv_alpha / (a / (us * us) + b)) <= -rate + k * log_rate - _lgamma(k + T(1.0), T)
+            acc = pending & (fast | (~rej & slow))
+            out[acc], att[acc] = k[acc], t
+            pending &= ~acc
+    return out, att
+
+
+# ------------------------------------------------------------------------------------------
+# compiler
+# ------------------------------------------------------------------------------------------
+def compile_predictive(model, args=(), kwargs=None, given=()):
+    """Trace ``model(*args, **kwargs)`` and lower its forward run to a PredictiveProgram.  The
+    sample sites without data whose name is in ``given`` are the inputs (sorted by name,
+    constrained values); every other site without data is drawn.  Raises NotImplementedError
+    naming the site for a model outside the program compiler's class."""
+    cfg = getattr(model, "_nmx_reparam", None)
+    fn = getattr(model, "_nmx_model", model)
+    trace = trace_model(fn, args, kwargs, cfg)
+    for name in trace.reparam:
+        _refuse(name, "reparam configs are not supported")
+    given = set(given)
+    sizes = {}
+    for s in trace.sites.values():
+        base = _base(s.fn)
+        if type(base) not in _DRAW:
+            _refuse(s.name, f"{type(base).__name__} is not supported")
+        if len(s.shape) > 1:
+            _refuse(s.name, f"site of shape {s.shape}: sites of rank > 1 are not supported")
+        if s.obs is not None and np.ndim(_host(s.obs)) > 1:
+            _refuse(s.name, f"observations of shape {np.shape(_host(s.obs))}: rank > 1 is not supported")
+        n = int(np.prod(s.shape, dtype=np.int64))
+        if n <= 0:
+            _refuse(s.name, "empty site")
+        sizes[s.name] = n
+    inputs, dim = [], 0
+    for s in sorted((s for s in trace.sites.values() if s.obs is None and s.name in given), key=lambda s: s.name):
+        inputs.append((s.name, dim, sizes[s.name], tuple(s.shape)))
+        dim += sizes[s.name]
+    B = _Builder(dim)
+    values = {name: _V(B, n, slot=off) for name, off, n, _ in inputs}
+    lower = _Lowering(B, values)
+    outputs, observed = [], {}
+    for s in trace.sites.values():
+        if s.obs is not None:
+            observed[s.name] = (s.obs, isinstance(_base(s.fn), _INTEGER))
+            continue
+        if s.name in values:
+            continue
+        base, n = _base(s.fn), sizes[s.name]
+        if n > native.DRAW_MAX_ELEMENTS:
+            _refuse(s.name, f"a drawn site of {n} elements (more than 2^24, the draw counter's element field)")
+        first = B.n_draws
+        try:
+            d = {p: lower(getattr(base, p), s.name) for p in _LOGPROB[type(base)][1]}
+            for p, val in d.items():
+                if val.n not in (1, n):
+                    _refuse(s.name, f"parameter {p!r} of {val.n} elements at a site of {n}")
+            val = _DRAW[type(base)](B, d, n)
+        except _Refuse:
+            raise
+        except NotImplementedError as e:
+            _refuse(s.name, str(e))
+        assert not val.is_const and val.n == n
+        values[s.name] = val
+        outputs.append(Output(s.name, val.slot, n, s.shape, isinstance(base, _INTEGER), range(first, B.n_draws)))
+    drawn = {o.name for o in outputs}
+    host_dets = {}
+    for name, expr in trace.deterministics.items():
+        if not (_sym_latents(expr, set()) & drawn):
+            host_dets[name] = expr  # given sites alone: evaluated from the samples (frontend.eval_sym)
+            continue
+        shape = tuple(shape_of(expr))
+        if len(shape) > 1:
+            _refuse(name, f"deterministic site of shape {shape}: rank > 1 is not supported")
+        val = lower(expr, name)
+        outputs.append(Output(name, val.slot, val.n, shape, False))
+    if not outputs:
+        # nothing to run on the device: every site is given or observed
+        return PredictiveProgram(np.zeros((0, native.OP_WORDS)), [], [], dim, dim, inputs, [], observed, host_dets)
+    made = {op[1]: k for k, op in enumerate(B.ops)}
+    ops, moved, num_slots = B.compact([made[o.slot] for o in outputs])
+    for o in outputs:
+        o.slot = moved[o.slot]
+    # stream ids are ordinals both before and after compaction: every draw feeds an output site
+    assert [op[7] for op in ops if op[0] >= native.DRAW_BASE] == list(range(B.n_draws))
+    consts = np.concatenate(B.consts) if B.consts else np.zeros(0)
+    return PredictiveProgram(ops, consts, B.index, num_slots, dim, inputs, outputs, observed, host_dets)

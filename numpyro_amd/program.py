@@ -255,6 +255,7 @@ class _Builder:
         self.memo = {}  # (op, operand keys) -> value: common subexpressions
         self.pool = {}  # constant bytes -> pool offset
         self.made_by = {}  # slot -> (op name, operand value) for the log(exp(x)) rewrite
+        self.n_draws = 0  # draw ops of a predictive program (predictive_program.py)
 
     def const(self, x):
         if isinstance(x, _V):
@@ -281,7 +282,7 @@ class _Builder:
             return self.memo[key]
         dst = self.next_slot
         self.next_slot += n_dst
-        self.ops.append([OPCODE[name], dst, a, b, n, sa, sb, aux])
+        self.ops.append([OPCODE[name] if name in OPCODE else native.DRAW_OPCODE[name], dst, a, b, n, sa, sb, aux])
         out = _V(self, n_dst, slot=dst)
         self.memo[key] = out
         return out
@@ -351,35 +352,63 @@ class _Builder:
     def unary(self, name):
         return lambda x: self.ew(name, x)
 
+    def draw(self, name, n, a=None):
+        """A draw op of n elements (predictive programs only): never shared, never folded.  The
+        stream id is the draw's ordinal."""
+        ra, sa = 0, 0
+        if a is not None:
+            a = self.const(a)
+            if a.n not in (1, n):
+                raise NotImplementedError(f"a parameter of {a.n} elements at a site of {n}")
+            ra, sa = self._ref(a), int(a.n == n)
+        stream = self.n_draws
+        self.n_draws += 1
+        return self._emit(name, n, ra, 0, n, sa, 0, stream, ("draw", stream))
+
     def program(self):
         """The ops the last one (U) depends on, renumbered so that each defines the next free slots."""
+        out, _, cursor = self.compact([len(self.ops) - 1])
+        consts = np.concatenate(self.consts) if self.consts else np.zeros(0)
+        return Program(out, consts, self.index, cursor, self.dim)
+
+    def compact(self, roots):
+        """(ops, old slot -> new slot, num_slots) of the ops that the ops `roots` depend on,
+        renumbered so that each defines the next free slots (draw ops: the next stream ids)."""
         ops, dim = self.ops, self.dim
         made = {o[1]: k for k, o in enumerate(ops)}
         binary = range(OPCODE["add"], OPCODE["reduce_sum"])
+        draws = native.DRAW_OPCODE
+
+        def fields(o):  # the words of an op that are operand references
+            if o[0] >= native.DRAW_BASE:
+                return (2,) if o[0] >= draws["draw_gamma"] else ()
+            return (2, 3) if o[0] in binary else (2,)
 
         def slot_refs(o):
-            return [r for r in ((o[2], o[3]) if o[0] in binary else (o[2],)) if r >= dim]
+            return [o[f] for f in fields(o) if o[f] >= dim]
 
-        live, todo = set(), [len(ops) - 1]
+        live, todo = set(), list(roots)
         while todo:
             k = todo.pop()
             if k not in live:
                 live.add(k)
                 todo += [made[r] for r in slot_refs(ops[k])]
-        moved, cursor, out = {}, dim, []
+        moved, cursor, out, n_draws = {}, dim, [], 0
         for k, o in enumerate(ops):
             if k not in live:
                 continue
             o = list(o)
-            for f in ((2, 3) if o[0] in binary else (2,)):
+            for f in fields(o):
                 if o[f] >= dim:
                     o[f] = moved[o[f]]
+            if o[0] >= native.DRAW_BASE:
+                o[7] = n_draws
+                n_draws += 1
             moved[o[1]] = cursor
             o[1] = cursor
             cursor += 1 if o[0] == OPCODE["reduce_sum"] else o[4]
             out.append(o)
-        consts = np.concatenate(self.consts) if self.consts else np.zeros(0)
-        return Program(out, consts, self.index, cursor, dim)
+        return out, moved, cursor
 
 
 # ------------------------------------------------------------------------------------------
