@@ -536,14 +536,16 @@ int nmx_predict_bnn(const float* X, int n, int dx, int dh, int dy, const float* 
  *      below and arithmetic (Normal = loc + scale * draw_normal, ...).  There is no U: the host
  *      reads each output site as a slice of the sample's tape row.
  *
- * A draw op is { opcode, dst, a, 0, n, sa, 0, stream }: a is the parameter (slot or constant,
- * stride sa in {0, 1}; 0 for the draws without one), n <= 2^24, `stream` the ordinal of the
+ * A draw op is { opcode, dst, a, b, n, sa, sb, stream }: a is the parameter (slot or constant,
+ * stride sa in {0, 1}; 0 for the draws without one), b / sb the second parameter of a draw with
+ * two (NMX_DRAW_BINOMIAL; 0 otherwise), n <= 2^24, `stream` the ordinal of the
  * draw op in the program (0, 1, ...).  Element i of sample s uses the Philox blocks
  *   w(t) = nmx_rng(seed, s, stream, NMX_EV_PREDICT = 7, i, t),  t = attempt = 0, 1, ...
  * (counter = (s, stream, 7 << 24 | i, t), s the global sample index), so a draw depends only on
  * (seed, sample, stream, element).  u01(x) = (x >> 8) 2^-24 in [0, 1), u01_open0(x) =
  * ((x >> 8) + 1) 2^-24 in (0, 1].  A parameter outside the support gives NaN without a loop;
- * every loop is bounded by NMX_DRAW_MAX_ATTEMPTS / NMX_POISSON_MAX_STEPS, exhausted -> NaN.
+ * every loop is bounded by NMX_DRAW_MAX_ATTEMPTS / NMX_POISSON_MAX_STEPS /
+ * NMX_BINOMIAL_MAX_STEPS, exhausted -> NaN.
  *   NMX_DRAW_NORMAL:      sqrt(-2 log u01_open0(w(0).x)) cos(2 pi u01(w(0).y))   (Box-Muller)
  *   NMX_DRAW_EXPONENTIAL: -log u01_open0(w(0).x)
  *   NMX_DRAW_CAUCHY:      tan(pi (((w(0).x >> 8) + 0.5) 2^-24 - 0.5))
@@ -562,18 +564,48 @@ int nmx_predict_bnn(const float* X, int n, int dx, int dh, int dy, const float* 
  *       v_r = 0.9277 - 3.6224 / (b - 2), us = 0.5 - |U|, k = floor((2 a / us + b) U + rate + 0.43);
  *       accepted when us >= 0.07 and V <= v_r; rejected when k < 0 or (us < 0.013 and V > us);
  *       else accepted when log(V / alpha / (a / us^2 + b)) <= -rate + k log rate - lgamma(k + 1).
+ *   NMX_DRAW_UNIFORM:     u01(w(0).x)
+ *   NMX_DRAW_BINOMIAL (a = total count n, b = probability p; the structure of
+ *     numpyro/distributions/util.py:20-181).  Before any loop: NaN when n or p is NaN, p is
+ *     outside [0, 1], or n is negative, not a whole number or >= 2^24 (every count up to n is
+ *     then an exact f32); 0 when p = 0 or n = 0; n when p = 1.  Else q = p > 0.5 ? 1 - p : p,
+ *     the count k of successes at probability q is drawn and the value is p > 0.5 ? n - k : k.
+ *     n q < 10: inversion of u = u01(w(0).x): the first k with u <= sum_{j <= k} f_j, f_0 =
+ *       exp(n log1p(-q)), f_j = f_{j-1} (n - j + 1) / j * (q / (1 - q)), or k = n, or the first
+ *       k > n q with f_k < 2^-40 (the tail left is below the 2^-24 resolution of u), k <
+ *       NMX_BINOMIAL_MAX_STEPS.  The bound: the count has mean below 10, so by Chernoff
+ *       P(X >= k) <= (10 e / k)^k, which is below 1e-50 at k = 96, far below 2^-24 = 6e-8: a
+ *       uniform that could reach step 96 does not exist, and f_k < 2^-40 ends the walk long
+ *       before (f_0 >= exp(-10 log(4)) = 9.5e-7, so nothing underflows on the way).
+ *     n q >= 10: Hoermann's BTRS (1993), attempt t with U = u01(w(t).x) - 0.5, V =
+ *       u01_open0(w(t).y): spq = sqrt(n q (1 - q)), c = n q + 0.5, b = 1.15 + 2.53 spq,
+ *       a = -0.0873 + 0.0248 b + 0.01 q, alpha = (2.83 + 5.1 / b) spq, v_r = 0.92 - 4.2 / b,
+ *       m = floor((n + 1) q), lq = log(q) - log1p(-q), us = 0.5 - |U|,
+ *       k = floor((2 a / us + b) U + c);
+ *       accepted when us >= 0.07 and V <= v_r; rejected unless 0 <= k <= n; else accepted when
+ *       log(V alpha / (a / us^2 + b)) <= (n + 1) log1p((k - m) / (n - k + 1))
+ *         + (k + 0.5) (log((n - k + 1) / (k + 1)) + lq) + (tail(k) - tail(n - k))
+ *         + (m + 0.5) (log((m + 1) / (n - m + 1)) - lq) + (tail(m) + tail(n - m)),
+ *       tail(j) = log(j!) - the Stirling formula at j + 1: a table of ten values for j < 10, else
+ *       (1/12 - (1/360 - 1/1260 / (j+1)^2) / (j+1)^2) / (j+1).  (log((n-m+1) / (n-k+1)) is taken
+ *       as log1p of an exact integer ratio: in f32 the direct form loses n ulp.)
  * ---- */
 enum nmx_draw_opcode {
   NMX_DRAW_NORMAL = 64, NMX_DRAW_EXPONENTIAL, NMX_DRAW_CAUCHY,  /* no parameter */
   NMX_DRAW_GAMMA, NMX_DRAW_BERNOULLI, NMX_DRAW_POISSON,         /* parameter a */
+  NMX_DRAW_UNIFORM,                                             /* no parameter */
+  NMX_DRAW_BINOMIAL,                                            /* parameters a, b */
   NMX_DRAW_END
 };
 #define NMX_DRAW_MAX_ATTEMPTS 64
 #define NMX_POISSON_MAX_STEPS 96
 #define NMX_POISSON_PTRS_RATE 10.0f
+#define NMX_BINOMIAL_MAX_STEPS 96
+#define NMX_BINOMIAL_BTRS_MEAN 10.0f
+#define NMX_BINOMIAL_MAX_COUNT 16777216.0f /* 2^24 */
 
 /* Validate a predictive program in HOST memory, as nmx_program_check does, with dim >= 0, draw
- * ops (parameter, count <= 2^24, stream id = ordinal) and no U; `outputs` is num_outputs x
+ * ops (parameters, count <= 2^24, stream id = ordinal) and no U; `outputs` is num_outputs x
  * { slot, n }: each must be a given site inside [0, dim) or lie inside one defined value.
  * Needs no GPU; names the bad op or output. */
 int nmx_predict_program_check(const nmx_program* host_program, const int32_t* outputs, int num_outputs);

@@ -235,8 +235,11 @@ struct NmxProgram {
 //   cauchy       tan(pi (mid24(w0.x) - 0.5))                  bernoulli    u01(w0.x) < p
 //   gamma        attempt t: normal of (wt.x, wt.y), accept uniform wt.z, boost uniform wt.w
 //   poisson      rate < 10: inversion of u01(w0.x); else PTRS, attempt t: (wt.x, wt.y)
-// Every loop has a compile-time bound (NMX_DRAW_MAX_ATTEMPTS, NMX_POISSON_MAX_STEPS) and a
-// parameter outside the support returns NaN before any loop: bad input cannot make a lane spin.
+//   uniform      u01(w0.x)
+//   binomial     q = min(p, 1 - p); n q < 10: inversion of u01(w0.x); else BTRS, attempt t: (wt.x, wt.y)
+// Every loop has a compile-time bound (NMX_DRAW_MAX_ATTEMPTS, NMX_POISSON_MAX_STEPS,
+// NMX_BINOMIAL_MAX_STEPS) and a parameter outside the support returns NaN before any loop: bad
+// input cannot make a lane spin.
 __device__ __forceinline__ float nmx_draw_normal(const nmx_u4& w) {
   float z, unused;
   nmx_box_muller(w.x, w.y, z, unused);
@@ -290,15 +293,75 @@ __device__ __forceinline__ float nmx_draw_poisson(float rate, uint64_t seed, uin
   return NAN;
 }
 
+// log(j!) minus the Stirling formula at j + 1 (Hoermann 1993, the f(k) of BTRS), j >= 0 whole
+static __device__ const float NMX_STIRLING_TAIL[10] = {
+    0.08106146679532726f, 0.04134069595540929f, 0.02767792568499834f, 0.02079067210376509f, 0.01664469118982119f,
+    0.01387612882307075f, 0.01189670994589177f, 0.01041126526197209f, 0.009255462182712733f, 0.008330563433362871f};
+
+__device__ __forceinline__ float nmx_stirling_tail(float j) {
+  if (j < 10.0f) return NMX_STIRLING_TAIL[(int)j];
+  const float r = 1.0f / (j + 1.0f), r2 = r * r;
+  return (1.0f / 12 - (1.0f / 360 - (1.0f / 1260) * r2) * r2) * r;
+}
+
+// Inlined like the other draws: k_program_predict keeps its occupancy (80 VGPRs, 6 waves / SIMD),
+// while the out-of-line form measured 106 VGPRs and 4 waves (DESIGN.md "Predictive programs").
+// lq is one live value where log q and log1p(-q) would be two: that register is the margin.
+__device__ __forceinline__ float nmx_draw_binomial(float n, float p, uint64_t seed, uint32_t s, uint32_t stream,
+                                                uint32_t i) {
+  if (!(p >= 0.0f && p <= 1.0f) || !(n >= 0.0f && n < NMX_BINOMIAL_MAX_COUNT) || n != floorf(n)) return NAN;
+  if (p == 0.0f || n == 0.0f) return 0.0f;
+  if (p == 1.0f) return n;
+  const bool mirror = p > 0.5f;
+  const float q = mirror ? 1.0f - p : p;
+  const float mu = n * q, log1_q = log1pf(-q);
+  if (mu < NMX_BINOMIAL_BTRS_MEAN) {
+    const float u = nmx_u01(nmx_rng(seed, s, stream, NMX_EV_PREDICT, i, 0).x);
+    const float odds = q / (1.0f - q);
+    float f = expf(n * log1_q), sum = f, k = 0.0f;
+    for (int step = 0; step < NMX_BINOMIAL_MAX_STEPS; ++step) {
+      if (u <= sum || k >= n) return mirror ? n - k : k;
+      k += 1.0f;
+      f = f * (n - k + 1.0f) / k * odds;
+      sum += f;
+      if (f < 0x1p-40f && k > mu) return mirror ? n - k : k;
+    }
+    return NAN;
+  }
+  const float lq = logf(q) - log1_q, spq = sqrtf(mu * (1.0f - q)), c = mu + 0.5f;
+  const float b = 1.15f + 2.53f * spq, a = -0.0873f + 0.0248f * b + 0.01f * q;
+  const float alpha = (2.83f + 5.1f / b) * spq, v_r = 0.92f - 4.2f / b;
+  const float m = floorf((n + 1.0f) * q);
+  const float log_h = (m + 0.5f) * (logf((m + 1.0f) / (n - m + 1.0f)) - lq) +
+                      (nmx_stirling_tail(m) + nmx_stirling_tail(n - m));
+  for (uint32_t t = 0; t < NMX_DRAW_MAX_ATTEMPTS; ++t) {
+    const nmx_u4 w = nmx_rng(seed, s, stream, NMX_EV_PREDICT, i, t);
+    const float U = nmx_u01(w.x) - 0.5f, V = nmx_u01_open0(w.y);
+    const float us = 0.5f - fabsf(U);
+    const float k = floorf((2.0f * a / us + b) * U + c);
+    if (us >= 0.07f && V <= v_r) return mirror ? n - k : k;
+    if (!(k >= 0.0f && k <= n)) continue;
+    const float log_f = (n + 1.0f) * log1pf((k - m) / (n - k + 1.0f)) +
+                        (k + 0.5f) * (logf((n - k + 1.0f) / (k + 1.0f)) + lq) +
+                        (nmx_stirling_tail(k) - nmx_stirling_tail(n - k)) + log_h;
+    if (logf(V * alpha / (a / (us * us) + b)) <= log_f) return mirror ? n - k : k;
+  }
+  return NAN;
+}
+
 struct NmxPredict {
   NmxProgram prog;  // p.dim = given coordinates; ws unused (the tape holds values only)
   uint64_t seed;
 
   __device__ __forceinline__ static bool is_draw(const NmxOp& o) { return o.op >= NMX_DRAW_NORMAL; }
-  __device__ __forceinline__ static bool has_param(const NmxOp& o) { return o.op >= NMX_DRAW_GAMMA; }
-  // the barrier rule of NmxProgram::reads_scalar_slot for a draw's parameter
+  __device__ __forceinline__ static bool has_param(const NmxOp& o) {
+    return o.op >= NMX_DRAW_GAMMA && o.op != NMX_DRAW_UNIFORM;
+  }
+  __device__ __forceinline__ static bool has_param_b(const NmxOp& o) { return o.op == NMX_DRAW_BINOMIAL; }
+  // the barrier rule of NmxProgram::reads_scalar_slot for a draw's parameters
   __device__ __forceinline__ static bool reads_scalar_slot(const NmxOp& o) {
-    return has_param(o) && o.a >= 0 && !o.sa && o.n != 1;
+    if (o.n == 1) return false;
+    return (has_param(o) && o.a >= 0 && !o.sa) || (has_param_b(o) && o.b >= 0 && !o.sb);
   }
 
   __device__ __forceinline__ void draw(const NmxOp& o, float* v, int lane, uint32_t s) const {
@@ -321,7 +384,11 @@ struct NmxPredict {
           r = (a >= 0.0f && a <= 1.0f) ? (nmx_u01(nmx_rng(seed, s, stream, NMX_EV_PREDICT, i, 0).x) < a ? 1.0f : 0.0f)
                                        : NAN;
           break;
-        default: r = nmx_draw_poisson(a, seed, s, stream, i); break;  // NMX_DRAW_POISSON
+        case NMX_DRAW_POISSON: r = nmx_draw_poisson(a, seed, s, stream, i); break;
+        case NMX_DRAW_UNIFORM: r = nmx_u01(nmx_rng(seed, s, stream, NMX_EV_PREDICT, i, 0).x); break;
+        default:  // NMX_DRAW_BINOMIAL
+          r = nmx_draw_binomial(a, prog.operand(v, o.b, i * o.sb), seed, s, stream, i);
+          break;
       }
       NMX_DCHECK(o.dst >= prog.p.dim && o.dst + i < prog.p.num_slots);
       v[o.dst + i] = r;

@@ -23,7 +23,8 @@ const char* const OP_NAMES[NMX_NUM_OPCODES] = {"neg", "exp", "log", "sqrt", "tan
                                                "lgamma", "add", "sub", "mul", "div", "pow", "reduce_sum",
                                                "gather", "matvec"};
 const char* const DRAW_NAMES[NMX_DRAW_END - NMX_DRAW_NORMAL] = {"draw_normal", "draw_exponential", "draw_cauchy",
-                                                                "draw_gamma", "draw_bernoulli", "draw_poisson"};
+                                                                "draw_gamma", "draw_bernoulli", "draw_poisson",
+                                                                "draw_uniform", "draw_binomial"};
 
 }  // namespace
 
@@ -65,12 +66,20 @@ int nmx_program_check_impl(const nmx_program* hp, bool predictive, const int32_t
       if (aux != num_draws)
         return nmx_fail(NMX_ERR_INVALID, "op %d (%s): stream id %d is not the draw's ordinal %d", k, nm, aux, num_draws);
       ++num_draws;
-      if (op >= NMX_DRAW_GAMMA) {
+      if (op >= NMX_DRAW_GAMMA && op != NMX_DRAW_UNIFORM) {
         if (sa != 0 && sa != 1) return nmx_fail(NMX_ERR_INVALID, "op %d (%s): stride %d not 0 or 1", k, nm, sa);
         const int64_t la = sa ? n : 1;
         if (a >= 0 ? !slot_ok(a, la) : !const_ok(a, la))
           return nmx_fail(NMX_ERR_INVALID, "op %d (%s): parameter %s %d (x%lld) out of range", k, nm,
                           a >= 0 ? "slot" : "constant", a >= 0 ? a : ~a, (long long)la);
+      }
+      if (op == NMX_DRAW_BINOMIAL) {
+        if (sb != 0 && sb != 1)
+          return nmx_fail(NMX_ERR_INVALID, "op %d (%s): second stride %d not 0 or 1", k, nm, sb);
+        const int64_t lb = sb ? n : 1;
+        if (b >= 0 ? !slot_ok(b, lb) : !const_ok(b, lb))
+          return nmx_fail(NMX_ERR_INVALID, "op %d (%s): second parameter %s %d (x%lld) out of range", k, nm,
+                          b >= 0 ? "slot" : "constant", b >= 0 ? b : ~b, (long long)lb);
       }
     } else if (op < NMX_OP_REDUCE_SUM) {
       const bool binary = op >= NMX_OP_ADD;

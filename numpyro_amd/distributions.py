@@ -8,7 +8,9 @@ log_prob into primitive operations), so there is no log_prob here.  Names and si
 Normal (continuous.py:2171), HalfCauchy (:700), Exponential (:455), Gamma (:490), StudentT
 (:2344), Bernoulli / BernoulliLogits (discrete.py:108-139), GaussianRandomWalk (continuous.py:
 658), MultivariateNormal (:1487), HalfNormal (:829), LogNormal (:1166), Cauchy (:217), Poisson
-(discrete.py:748; observed sites only); ``.to_event`` / ``.expand`` (distribution.py:377-420).
+(discrete.py:748; observed sites only), Uniform (continuous.py:2431), Beta (:165), Pareto (:2230),
+BinomialProbs / BinomialLogits / Binomial (discrete.py:172, :243, :298; observed sites only);
+``.to_event`` / ``.expand`` (distribution.py:377-420).
 """
 from __future__ import annotations
 
@@ -191,6 +193,76 @@ def Bernoulli(probs=None, logits=None):
     if (probs is None) == (logits is None):
         raise ValueError("One of `probs` or `logits` must be specified.")
     return BernoulliLogits(logits) if logits is not None else BernoulliProbs(probs)
+
+
+class Uniform(Distribution):
+    """``support`` is "interval"; the bounds are ``low`` and ``high``."""
+
+    support = "interval"
+
+    def __init__(self, low=0.0, high=1.0):
+        super().__init__(_bshape(low, high))
+        self.low, self.high = low, high
+
+    def params(self):
+        return {"low": self.low, "high": self.high}
+
+
+class Beta(Distribution):
+    support = "unit_interval"
+
+    def __init__(self, concentration1, concentration0):
+        super().__init__(_bshape(concentration1, concentration0))
+        self.concentration1, self.concentration0 = concentration1, concentration0
+
+    def params(self):
+        return {"concentration1": self.concentration1, "concentration0": self.concentration0}
+
+
+class Pareto(Distribution):
+    """``support`` is "greater_than"; the lower bound is ``scale``."""
+
+    support = "greater_than"
+
+    def __init__(self, scale, alpha):
+        super().__init__(_bshape(scale, alpha))
+        self.scale, self.alpha = scale, alpha
+
+    def params(self):
+        return {"scale": self.scale, "alpha": self.alpha}
+
+
+class BinomialProbs(Distribution):
+    """Observed sites only (a discrete latent cannot be sampled by HMC)."""
+
+    support = "integer_interval"
+
+    def __init__(self, probs, total_count=1):
+        super().__init__(_bshape(probs, total_count))
+        self.probs, self.total_count = probs, total_count
+
+    def params(self):
+        return {"probs": self.probs, "total_count": self.total_count}
+
+
+class BinomialLogits(Distribution):
+    """Observed sites only (a discrete latent cannot be sampled by HMC)."""
+
+    support = "integer_interval"
+
+    def __init__(self, logits, total_count=1):
+        super().__init__(_bshape(logits, total_count))
+        self.logits, self.total_count = logits, total_count
+
+    def params(self):
+        return {"logits": self.logits, "total_count": self.total_count}
+
+
+def Binomial(total_count=1, probs=None, logits=None):
+    """numpyro/distributions/discrete.py:298-303 dispatch on probs / logits."""
+    if (probs is None) == (logits is None):
+        raise ValueError("One of `probs` or `logits` must be specified.")
+    return BinomialLogits(logits, total_count) if logits is not None else BinomialProbs(probs, total_count)
 
 
 class GaussianRandomWalk(Distribution):

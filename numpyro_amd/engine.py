@@ -444,13 +444,20 @@ class Engine:
 
     def _positive(self):
         """Coordinates the collection maps through exp (ExpTransform sites), as a bool mask."""
-        pos = self.model_potential.transform_codes().to(torch.bool)
+        from .potentials import POSITIVE
+
+        pos = self.model_potential.transform_codes() == POSITIVE
         return pos if self.constrain_samples else torch.zeros_like(pos)
 
     def _collect_codes(self):
-        """Transform codes the step kernels apply to collected draws (all zero: unconstrained)."""
+        """Transform codes the step kernels apply to collected draws (zero: unconstrained, for
+        every coordinate when constrain_samples is off and always for the codes above POSITIVE,
+        which Potential.constrain completes on the host side)."""
+        from .potentials import POSITIVE
+
         tr = self.potential.transform_codes()
-        return tr if self.constrain_samples else torch.zeros_like(tr)
+        keep = (tr == POSITIVE) if self.constrain_samples else torch.zeros_like(tr, dtype=torch.bool)
+        return torch.where(keep, tr, torch.zeros_like(tr))
 
     def _convert_slots(self, samples, slots, s):
         """In place: whitened draws of collection slots -> model space -> constrained."""

@@ -16,7 +16,7 @@ the model to the program compiler (numpyro_amd/program.py compile_model), which 
 traced log-joint to a straight-line program of primitive operations evaluated, with its
 reverse-mode adjoint, by one HIP kernel (csrc/potential_program.hip).  A model that matches a
 fused kernel always gets it; a model outside the program compiler's class (rank-2 latents,
-bounded supports, reparam configs, operations outside numpyro_amd.jnp) is refused by both.
+simplex supports, reparam configs, operations outside numpyro_amd.jnp) is refused by both.
 """
 from __future__ import annotations
 
@@ -318,7 +318,7 @@ def potential_from_model(model, args=(), kwargs=None):
 
 # ----------------------------------------------------------------------------- deterministic sites
 _SYM_UNARY = {"tanh": "tanh", "exp": "exp", "sqrt": "sqrt", "log": "log", "neg": "neg", "log1p": "log1p",
-              "square": "square"}
+              "square": "square", "expit": "sigmoid"}
 _SYM_OTHER = ("matmul", "sum", "getitem")
 _SYM_BINARY = {"add": "add", "sub": "sub", "mul": "mul", "div": "div", "pow": "pow"}
 

@@ -429,18 +429,12 @@ class HMC(MCMCKernel):
     def postprocess_fn(self, model_args=(), model_kwargs=None):
         """Unconstrained site values -> constrained ones plus deterministic sites
         (infer/util.py:176-190 constrain_fn)."""
-        import torch
-
-        from ..potentials import POSITIVE
-
         pot = self.potential(model_args, model_kwargs)
 
         def fn(z):
             if not isinstance(z, dict):
                 z = pot.unflatten(z)
-            out = {}
-            for name, _, tr in pot.sites:
-                out[name] = torch.exp(z[name]) if tr == POSITIVE else z[name]
+            out = pot.constrain(z)
             out.update(pot.deterministic(out))
             return out
 

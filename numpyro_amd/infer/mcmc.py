@@ -382,12 +382,6 @@ class MCMC:
         C = self.local_chains
         S = self._samples.shape[0]
         flat = self._samples[:, :, :C].permute(2, 0, 1)  # [C, S, D]
-        if getattr(self, "_host_constrain", False):
-            from ..potentials import POSITIVE
-
-            codes = pot.transform_codes().to(flat.device)
-            if bool((codes == POSITIVE).any()):
-                flat = torch.where(codes == POSITIVE, torch.exp(flat), flat)
         out = pot.unflatten(flat)
         if self.postprocess_fn is not None:
             # draws are unconstrained here (Engine.constrain_samples = False)
@@ -395,8 +389,12 @@ class MCMC:
             out = _postprocess_per_draw(self.postprocess_fn, out)
             if not include_deterministic:  # print_summary keeps the sample sites (mcmc.py:748-758)
                 out = {k: v for k, v in out.items() if k in names}
-        elif include_deterministic:
-            out.update(pot.deterministic(out))
+        else:
+            # the device collection has applied exp, unless the draws were kept unconstrained for
+            # z_grad; the sigmoid / lower-bound sites are always completed here
+            out = pot.constrain(out, device_exp=not getattr(self, "_host_constrain", False))
+            if include_deterministic:
+                out.update(pot.deterministic(out))
         if not group_by_chain:
             out = {k: v.reshape(C * S, *v.shape[2:]) for k, v in out.items()}
         return out

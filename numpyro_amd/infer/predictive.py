@@ -27,8 +27,8 @@ posterior sample (csrc/predictive_program.hip).  The sample sites named in ``pos
 are the program's inputs; every other site without data is drawn, in the model's order, so a
 drawn site parameterises the later ones.  ``Predictive(model, num_samples=N)`` without posterior
 samples draws every site: prior predictive.  Returned by default: the drawn sites, the observed
-sites whose data was passed (as given) and the deterministic sites; Bernoulli and Poisson sites
-as int32 (an element whose parameter is outside the support, where a float site holds NaN, is
+sites whose data was passed (as given) and the deterministic sites; Bernoulli, Binomial and Poisson
+sites as int32 (an element whose parameter is outside the support, where a float site holds NaN, is
 -1), the others float32.  A model outside the compiler's class raises NotImplementedError
 naming the site.
 """

@@ -1,5 +1,5 @@
 """The array functions the reference's example models call on jax.numpy (matmul, dot, tanh,
-exp, log, log1p, sqrt, square, sum, zeros, ones, shape; indexing a vector), working on NumPy / torch arrays and on the symbolic values of
+exp, log, log1p, sqrt, square, expit, sum, zeros, ones, shape; indexing a vector), working on NumPy / torch arrays and on the symbolic values of
 latent sites while the model front end traces a model (numpyro_amd/frontend.py).  Write
 ``from numpyro_amd import jnp`` where a numpyro model has ``import jax.numpy as jnp``."""
 from __future__ import annotations
@@ -87,6 +87,16 @@ sqrt = _unary("sqrt", np.sqrt)
 log = _unary("log", np.log)
 log1p = _unary("log1p", np.log1p)
 square = _unary("square", np.square)
+
+
+def _expit_host(x):
+    x = np.asarray(x, np.float64)
+    with np.errstate(over="ignore"):
+        return np.exp(-(np.maximum(-x, 0.0) + np.log1p(np.exp(-np.abs(x)))))  # exp(-softplus(-x))
+
+
+# jax.scipy.special.expit (the logistic sigmoid), as examples/ucbadmit.py and proportion_test.py use it
+expit = _unary("expit", _expit_host)
 
 
 def sum(x, axis=None):  # noqa: A001  (jax.numpy's name)

@@ -115,11 +115,15 @@ OP_WORDS = 8  # NMX_OP_WORDS: opcode, dst, a, b, n, sa, sb, aux
 
 # enum nmx_draw_opcode: the draw ops of a predictive program, apart from the arithmetic opcodes
 DRAW_BASE = 64
-DRAW_OPCODES = ["draw_normal", "draw_exponential", "draw_cauchy", "draw_gamma", "draw_bernoulli", "draw_poisson"]
+DRAW_OPCODES = ["draw_normal", "draw_exponential", "draw_cauchy", "draw_gamma", "draw_bernoulli", "draw_poisson",
+                "draw_uniform", "draw_binomial"]
 DRAW_OPCODE = {n: DRAW_BASE + i for i, n in enumerate(DRAW_OPCODES)}
 DRAW_MAX_ATTEMPTS = 64  # NMX_DRAW_MAX_ATTEMPTS
 POISSON_MAX_STEPS = 96  # NMX_POISSON_MAX_STEPS
 POISSON_PTRS_RATE = 10.0  # NMX_POISSON_PTRS_RATE
+BINOMIAL_MAX_STEPS = 96  # NMX_BINOMIAL_MAX_STEPS
+BINOMIAL_BTRS_MEAN = 10.0  # NMX_BINOMIAL_BTRS_MEAN
+BINOMIAL_MAX_COUNT = 1 << 24  # NMX_BINOMIAL_MAX_COUNT
 DRAW_MAX_ELEMENTS = 1 << 24  # the counter's element field
 
 

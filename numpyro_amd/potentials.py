@@ -23,13 +23,21 @@ from . import native
 from .native import check, lib, ptr
 
 REAL, POSITIVE = 0, 1  # transform codes: identity, ExpTransform (transforms.py:537-577)
+# x = sigmoid(u) (SigmoidTransform, transforms.py:950) and x = lo + exp(u) (the greater_than
+# bijection, transforms.py:1671-1680), each followed by the site's affine part
+# (``Potential.affine``).  The step kernels collect coordinates of these codes unconstrained;
+# ``Potential.constrain`` completes the transform in torch.
+UNIT, LOWER = 2, 3
 
 
 class Potential:
-    """Base class.  Subclasses set ``sites`` = [(name, shape, transform)] and ``dim``."""
+    """Base class.  Subclasses set ``sites`` = [(name, shape, transform)] and ``dim``;
+    ``affine`` = {name: (lo, width)} holds the affine part x = lo + width * f(u) of a UNIT or
+    LOWER site (a site without an entry has lo = 0, width = 1)."""
 
     sites: list = []
     dim: int = 0
+    affine: dict = {}
 
     def bind(self, num_chains: int, ldc: int, device) -> None:
         before = dict(self.__dict__)
@@ -72,6 +80,25 @@ class Potential:
     def deterministic(self, sites):
         """Deterministic sites computed from the sampled ones ({} unless the model has any)."""
         return {}
+
+    def constrain(self, sites, device_exp=False):
+        """{site: unconstrained values} -> {site: constrained values}.  ``device_exp``: the
+        values come from the device collection, which has already mapped the POSITIVE sites
+        through exp (and left every other code unconstrained)."""
+        out = {}
+        for name, _, tr in self.sites:
+            v = sites[name]
+            if tr == POSITIVE:
+                v = v if device_exp else torch.exp(v)
+            elif tr == UNIT:
+                v = torch.sigmoid(v)  # the stable form: exp is only taken of -|u|
+            elif tr == LOWER:
+                v = torch.exp(v)
+            if tr >= UNIT and name in self.affine:
+                lo, width = (torch.as_tensor(np.asarray(b), dtype=v.dtype, device=v.device) for b in self.affine[name])
+                v = lo + width * v
+            out[name] = v
+        return out
 
     def unflatten(self, flat):
         """[..., D] -> {site: [..., *shape]} (ravel_pytree order)."""

@@ -7,7 +7,8 @@ substituted and every other site sampled (numpyro/infer/util.py:803-885 _predict
 to a straight-line program of the program compiler's format (numpyro_amd/program.py, the same
 builder: folding, sharing and refusals are the same) in which a site that is neither observed
 nor given is *drawn*: a draw op fills its slots with base variates (standard normal, exponential,
-Cauchy; gamma(concentration), Bernoulli(probs), Poisson(rate)) and the existing arithmetic ops
+Cauchy, uniform; gamma(concentration), Bernoulli(probs), Poisson(rate); Binomial(total_count,
+probs), the one draw with two parameters) and the existing arithmetic ops
 build the distribution from them (``_DRAW``).  A drawn site's value then parameterises the later
 sites, so prior predictive of a hierarchical model runs ``mu -> theta -> obs`` in one program.
 One HIP kernel (csrc/predictive_program.hip) runs the program once per posterior sample.
@@ -85,14 +86,48 @@ def _dr_poisson(B, d, n):
     return B.draw("draw_poisson", n, d["rate"])
 
 
+def _dr_uniform(B, d, n):
+    return d["low"] + (d["high"] - d["low"]) * B.draw("draw_uniform", n)
+
+
+def _dr_pareto(B, d, n):
+    # scale exp(E / alpha), E standard exponential (continuous.py:2230 Pareto as a transformed Exponential)
+    return d["scale"] * B.ew("exp", B.draw("draw_exponential", n) / d["alpha"])
+
+
+def _dr_beta(B, d, n):
+    # g1 / (g1 + g0) of two gamma draws; where both underflow to 0 (concentrations far below 1)
+    # this is 0 / 0 = NaN (DESIGN.md "Predictive programs")
+    g1 = B.draw("draw_gamma", n, d["concentration1"])
+    g0 = B.draw("draw_gamma", n, d["concentration0"])
+    return g1 / (g1 + g0)
+
+
+def _binomial_count(d):
+    n = d["total_count"]
+    if n.is_const and np.any(n.c >= native.BINOMIAL_MAX_COUNT):
+        raise NotImplementedError(f"a total_count of {n.c.max():g} (2^24 or more: counts are float32 whole numbers)")
+    return n
+
+
+def _dr_binomial_probs(B, d, n):
+    return B.draw("draw_binomial", n, _binomial_count(d), d["probs"])
+
+
+def _dr_binomial_logits(B, d, n):
+    return B.draw("draw_binomial", n, _binomial_count(d), 1.0 / (1.0 + B.ew("exp", -d["logits"])))
+
+
 _DRAW = {
     dist.Normal: _dr_normal, dist.StudentT: _dr_student_t, dist.Cauchy: _dr_cauchy,
     dist.HalfCauchy: _dr_half_cauchy, dist.HalfNormal: _dr_half_normal, dist.LogNormal: _dr_log_normal,
     dist.Exponential: _dr_exponential, dist.Gamma: _dr_gamma, dist.BernoulliLogits: _dr_bernoulli_logits,
     dist.BernoulliProbs: _dr_bernoulli_probs, dist.Poisson: _dr_poisson,
+    dist.Uniform: _dr_uniform, dist.Beta: _dr_beta, dist.Pareto: _dr_pareto,
+    dist.BinomialProbs: _dr_binomial_probs, dist.BinomialLogits: _dr_binomial_logits,
 }
 assert set(_DRAW) == set(_LOGPROB)
-_INTEGER = (dist.BernoulliLogits, dist.BernoulliProbs, dist.Poisson)
+_INTEGER = (dist.BernoulliLogits, dist.BernoulliProbs, dist.Poisson, dist.BinomialProbs, dist.BinomialLogits)
 
 
 class Output:
@@ -208,12 +243,16 @@ class PredictiveProgram(Program):
                     M = cp[~b:~b + n * aux].reshape(n, aux)
                     v[:, dst:dst + n] = v[:, a:a + aux] @ M.T
                 else:
-                    par = None if nm in ("draw_normal", "draw_exponential", "draw_cauchy") else \
-                        np.broadcast_to(operand(a, n, sa), (S, n))
-                    out, att = _host_draw(nm, par, lambda t, k=aux, m=n: blocks(k, m, t), (S, n), T)
+                    par = None if nm in _NO_PARAM else np.broadcast_to(operand(a, n, sa), (S, n))
+                    if nm == "draw_binomial":
+                        par = (par, np.broadcast_to(operand(b, n, sb), (S, n)))
+                    steps = {}
+                    out, att = _host_draw(nm, par, lambda t, k=aux, m=n: blocks(k, m, t), (S, n), T, steps)
                     v[:, dst:dst + n] = out
                     if info is not None:
                         info[aux] = att
+                        if steps:  # the inversion walk's step count per element (binomial)
+                            info[("steps", aux)] = steps["steps"]
         return {o.name: v[:, o.slot:o.slot + o.n].reshape((S,) + o.shape).copy() for o in self.outputs}
 
 
@@ -236,10 +275,17 @@ def _box_muller(w, T):
     return rad * np.cos(T(6.283185307179586) * _u01(w[..., 1], T))
 
 
-def _host_draw(name, par, blocks, shape, T):
+_NO_PARAM = ("draw_normal", "draw_exponential", "draw_cauchy", "draw_uniform")
+
+
+def _host_draw(name, par, blocks, shape, T, steps=None):
     """(values, accepted attempt) of one draw op over [S, n]; `blocks(t)` are attempt t's words."""
     nan = T(np.nan)
     att = np.zeros(shape, np.int32)
+    if name == "draw_uniform":
+        return _u01(blocks(0)[..., 0], T), att
+    if name == "draw_binomial":
+        return _host_binomial(par[0], par[1], blocks, T, steps)
     if name == "draw_normal":
         return _box_muller(blocks(0), T), att
     if name == "draw_exponential":
@@ -327,6 +373,98 @@ def _host_poisson(rate, blocks, T):
             acc = pending & (fast | (~rej & slow))
             out[acc], att[acc] = k[acc], t
             pending &= ~acc
+    return out, att
+
+
+_STIRLING_TAIL = (0.08106146679532726, 0.04134069595540929, 0.02767792568499834, 0.02079067210376509,
+                  0.01664469118982119, 0.01387612882307075, 0.01189670994589177, 0.01041126526197209,
+                  0.009255462182712733, 0.008330563433362871)
+
+
+def _stirling_tail(j, T):
+    """log(j!) minus the Stirling formula at j + 1 (j >= 0 whole): table below 10, else the series."""
+    table = np.asarray(_STIRLING_TAIL, T)
+    small = j < T(10.0)
+    r = T(1.0) / (np.where(small, T(10.0), j) + T(1.0))
+    r2 = r * r
+    series = (T(1.0) / T(12) - (T(1.0) / T(360) - (T(1.0) / T(1260)) * r2) * r2) * r
+    return np.where(small, table[np.where(small, j, 0).astype(np.int64)], series)
+
+
+def _host_binomial(n, p, blocks, T, steps=None):
+    """q = min(p, 1 - p); n q < 10: inversion of one uniform; else Hoermann's BTRS (1993), one
+    block per attempt (include/numpyro_amd.h NMX_DRAW_BINOMIAL states the assignment)."""
+    ok = (p >= 0) & (p <= 1) & (n >= 0) & (n < T(native.BINOMIAL_MAX_COUNT)) & (n == np.floor(n))
+    out = np.full(n.shape, np.nan, T)
+    att = np.full(n.shape, -1, np.int32)
+    walked = np.zeros(n.shape, np.int32)
+    fixed = ok & ((p == 0) | (n == 0))
+    out[fixed], att[fixed] = 0, 0
+    fixed = ok & (p == 1) & (n != 0)
+    out[fixed], att[fixed] = n[fixed], 0
+    live = ok & (p > 0) & (p < 1) & (n > 0)
+    mirror = p > T(0.5)
+    q = np.where(live, np.where(mirror, T(1.0) - p, p), T(0.25)).astype(T)
+    nn = np.where(live, n, T(1.0)).astype(T)
+    mu, log1_q = nn * q, np.log1p(-q)
+
+    def put(mask, k):
+        out[mask] = np.where(mirror, nn - k, k)[mask]
+
+    small = live & (mu < T(native.BINOMIAL_BTRS_MEAN))
+    if small.any():
+        u = _u01(blocks(0)[..., 0], T)
+        odds = q / (T(1.0) - q)
+        f = np.exp(nn * log1_q)
+        total = f.copy()
+        k = np.zeros(n.shape, T)
+        pending = small.copy()
+        for _ in range(native.BINOMIAL_MAX_STEPS):
+            done = pending & ((u <= total) | (k >= nn))
+            put(done, k)
+            att[done] = 0
+            pending &= ~done
+            if not pending.any():
+                break
+            walked[pending] += 1
+            k = k + T(1.0)
+            f = f * (nn - k + T(1.0)) / k * odds
+            total = total + f
+            done = pending & (f < T(2.0 ** -40)) & (k > mu)
+            put(done, k)
+            att[done] = 0
+            pending &= ~done
+    pending = live & ~small
+    if pending.any():
+        lq = np.log(q) - log1_q
+        spq, c = np.sqrt(mu * (T(1.0) - q)), mu + T(0.5)
+        b = T(1.15) + T(2.53) * spq
+        a = T(-0.0873) + T(0.0248) * b + T(0.01) * q
+        alpha, v_r = (T(2.83) + T(5.1) / b) * spq, T(0.92) - T(4.2) / b
+        m = np.floor((nn + T(1.0)) * q)
+        log_h = (m + T(0.5)) * (np.log((m + T(1.0)) / (nn - m + T(1.0))) - lq) + \
+            (_stirling_tail(m, T) + _stirling_tail(nn - m, T))
+        for t in range(native.DRAW_MAX_ATTEMPTS):
+            if not pending.any():
+                break
+            w = blocks(t)
+            U = _u01(w[..., 0], T) - T(0.5)
+            V = _u01_open0(w[..., 1], T)
+            us = T(0.5) - np.abs(U)
+            k = np.floor((T(2.0) * a / us + b) * U + c)
+            fast = (us >= T(0.07)) & (V <= v_r)
+            inside = (k >= 0) & (k <= nn)
+            kk = np.where(inside, k, m)
+            log_f = (nn + T(1.0)) * np.log1p((kk - m) / (nn - kk + T(1.0))) + \
+                (kk + T(0.5)) * (np.log((nn - kk + T(1.0)) / (kk + T(1.0))) + lq) + \
+                (_stirling_tail(kk, T) - _stirling_tail(nn - kk, T)) + log_h
+            slow = np.log(V * alpha / (a / (us * us) + b)) <= log_f
+            acc = pending & (fast | (inside & slow))
+            put(acc, k)
+            att[acc] = t
+            pending &= ~acc
+    if steps is not None:
+        steps["steps"] = walked
     return out, att
 
 

@@ -13,15 +13,18 @@ and deterministic sites work as for the fused kernels.
 The kernel knows nothing about distributions: a new distribution is a ``_LOGPROB`` entry here.
 Host passes: subexpressions without a latent are folded in float64 into the constant pool
 (every normalising constant ends there), common subexpressions are shared (a ``Sym`` used twice
-is one value), ``log(exp(x))`` is ``x``.  ``Program.run_host`` is a float64 NumPy interpreter
+is one value), ``log(exp(x))`` is ``x``, ``log1p(-x)`` of a unit-interval site's own value is
+``-softplus(u)``.  ``Program.run_host`` is a float64 NumPy interpreter
 of the same program, forward and reverse: it defines the kernel's semantics op by op.
 
-Model class: latent sites of rank 0 or 1 with support ``real`` or ``positive`` (the kernel
-sees u = log x and the program adds -sum(u), as NmxEightSchools does) from Normal, StudentT,
-Cauchy, HalfCauchy, HalfNormal, LogNormal, Exponential, Gamma; observed sites from those plus
-BernoulliLogits / BernoulliProbs / Poisson; parameters that are constants or expressions of
-latents over numpyro_amd.jnp's operations.  Anything else raises NotImplementedError naming
-the site.
+Model class: latent sites of rank 0 or 1 with support ``real``, ``positive`` (the kernel
+sees u = log x and the program adds -sum(u), as NmxEightSchools does), ``unit_interval`` /
+``interval`` (x = lo + width sigmoid(u), built from -softplus(-u) and -softplus(u)) or
+``greater_than`` (x = lo + exp(u)), with constant bounds, from Normal, StudentT, Cauchy,
+HalfCauchy, HalfNormal, LogNormal, Exponential, Gamma, Uniform, Beta, Pareto; observed sites from
+those plus BernoulliLogits / BernoulliProbs / Poisson / BinomialLogits / BinomialProbs (with a
+total_count that is data); parameters that are constants or expressions of latents over
+numpyro_amd.jnp's operations.  Anything else raises NotImplementedError naming the site.
 """
 from __future__ import annotations
 
@@ -35,7 +38,7 @@ from . import native
 from .frontend import _base, _host, _with_traced_deterministics, trace_model
 from .jnp import Sym
 from .native import OPCODE
-from .potentials import POSITIVE, REAL, Potential
+from .potentials import LOWER, POSITIVE, REAL, UNIT, Potential
 
 _UNARY = ("neg", "exp", "log", "sqrt", "tanh", "log1p", "square", "softplus", "lgamma")
 _BINARY = ("add", "sub", "mul", "div", "pow")
@@ -133,13 +136,15 @@ class Program:
                 for k, o in enumerate(self.ops.tolist())]
 
     # ------------------------------------------------------------------ float64 interpreter
-    def run_host(self, Z):
+    def run_host(self, Z, f32_consts=False):
         """(U [C], dU/dz [C, D]) of the rows of Z [C, D], in float64: the program forward and
-        reverse, op by op as the kernel runs it (only the order inside sums differs)."""
+        reverse, op by op as the kernel runs it (only the order inside sums differs).
+        ``f32_consts``: with the constant pool rounded to float32, as the device holds it."""
         Z = np.atleast_2d(np.asarray(Z, np.float64))
         C, S, D = Z.shape[0], self.num_slots, self.dim
         assert Z.shape[1] == D
-        cp, ix, names = self.consts64, self.index, native.OPCODES
+        cp = self.consts.astype(np.float64) if f32_consts else self.consts64
+        ix, names = self.index, native.OPCODES
         v = np.zeros((C, S))
         g = np.zeros((C, S))
         v[:, :D] = Z
@@ -255,6 +260,7 @@ class _Builder:
         self.memo = {}  # (op, operand keys) -> value: common subexpressions
         self.pool = {}  # constant bytes -> pool offset
         self.made_by = {}  # slot -> (op name, operand value) for the log(exp(x)) rewrite
+        self.log1m = {}  # slot of a unit site's value x -> log(1 - x), for the log1p(-x) rewrite
         self.n_draws = 0  # draw ops of a predictive program (predictive_program.py)
 
     def const(self, x):
@@ -306,6 +312,15 @@ class _Builder:
                 return b
         if name == "log" and self.made_by.get(a.slot, ("",))[0] == "exp":
             return self.made_by[a.slot][1]
+        # log1p(-x) of a unit site's own value x = sigmoid(u) is -softplus(u): the direct form is
+        # -inf in float32 from u of about 17
+        if name == "log1p" and self.made_by.get(a.slot, ("",))[0] == "neg" \
+                and self.made_by[a.slot][1].slot in self.log1m:
+            return self.log1m[self.made_by[a.slot][1].slot]
+        # ... and 1 - x of it is sigmoid(-u) = exp(-softplus(u)): in float32 the subtraction is a
+        # multiple of 2^-24, wrong by half from u of about 16 (Beta(m kappa, (1 - m) kappa))
+        if name == "sub" and a.is_const and np.all(a.c == 1.0) and b.slot in self.log1m and b.n == n:
+            return self.ew("exp", self.log1m[b.slot])
         # x + (-y) is x - y (log densities are written as sums of negated terms); the negation
         # left without a reader is dropped by program()
         if name == "add" and not b.is_const and self.made_by.get(b.slot, ("",))[0] == "neg":
@@ -352,18 +367,21 @@ class _Builder:
     def unary(self, name):
         return lambda x: self.ew(name, x)
 
-    def draw(self, name, n, a=None):
+    def draw(self, name, n, a=None, b=None):
         """A draw op of n elements (predictive programs only): never shared, never folded.  The
         stream id is the draw's ordinal."""
-        ra, sa = 0, 0
-        if a is not None:
-            a = self.const(a)
-            if a.n not in (1, n):
-                raise NotImplementedError(f"a parameter of {a.n} elements at a site of {n}")
-            ra, sa = self._ref(a), int(a.n == n)
+        refs = []
+        for par in (a, b):
+            if par is None:
+                refs += [0, 0]
+                continue
+            par = self.const(par)
+            if par.n not in (1, n):
+                raise NotImplementedError(f"a parameter of {par.n} elements at a site of {n}")
+            refs += [self._ref(par), int(par.n == n)]
         stream = self.n_draws
         self.n_draws += 1
-        return self._emit(name, n, ra, 0, n, sa, 0, stream, ("draw", stream))
+        return self._emit(name, n, refs[0], refs[2], n, refs[1], refs[3], stream, ("draw", stream))
 
     def program(self):
         """The ops the last one (U) depends on, renumbered so that each defines the next free slots."""
@@ -381,7 +399,9 @@ class _Builder:
 
         def fields(o):  # the words of an op that are operand references
             if o[0] >= native.DRAW_BASE:
-                return (2,) if o[0] >= draws["draw_gamma"] else ()
+                if o[0] == draws["draw_binomial"]:
+                    return (2, 3)
+                return (2,) if o[0] >= draws["draw_gamma"] and o[0] != draws["draw_uniform"] else ()
             return (2, 3) if o[0] in binary else (2,)
 
         def slot_refs(o):
@@ -471,6 +491,39 @@ def _lp_poisson(B, d, x, logx):
     return [x * B.ew("log", d["rate"]), -d["rate"], -B.ew("lgamma", x + 1.0)]
 
 
+def _lp_uniform(B, d, x, logx):
+    return [-B.ew("log", d["high"] - d["low"])]
+
+
+def _lp_beta(B, d, x, logx):
+    # at a latent site x is the site's own sigmoid: log(x) is logx and log1p(-x) resolves to
+    # -softplus(u) (_Builder.ew), neither is formed from x
+    a, b = d["concentration1"], d["concentration0"]
+    logx = B.ew("log", x) if logx is None else logx
+    return [(a - 1.0) * logx, (b - 1.0) * B.ew("log1p", -x),
+            B.ew("lgamma", a + b) - B.ew("lgamma", a) - B.ew("lgamma", b)]
+
+
+def _lp_pareto(B, d, x, logx):
+    alpha = d["alpha"]
+    return [B.ew("log", alpha), alpha * B.ew("log", d["scale"]), -((alpha + 1.0) * B.ew("log", x))]
+
+
+def _binomial_coefficient(B, n, k):
+    # data alone: folded on the host
+    return B.ew("lgamma", n + 1.0) - B.ew("lgamma", k + 1.0) - B.ew("lgamma", n - k + 1.0)
+
+
+def _lp_binomial_probs(B, d, x, logx):
+    n, p = d["total_count"], d["probs"]
+    return [x * B.ew("log", p), (n - x) * B.ew("log1p", -p), _binomial_coefficient(B, n, x)]
+
+
+def _lp_binomial_logits(B, d, x, logx):
+    n = d["total_count"]
+    return [x * d["logits"], -(n * B.ew("softplus", d["logits"])), _binomial_coefficient(B, n, x)]
+
+
 # distribution -> (expansion, parameter names, may be latent)
 _LOGPROB = {
     dist.Normal: (_lp_normal, ("loc", "scale"), True),
@@ -484,7 +537,37 @@ _LOGPROB = {
     dist.BernoulliLogits: (_lp_bernoulli_logits, ("logits",), False),
     dist.BernoulliProbs: (_lp_bernoulli_probs, ("probs",), False),
     dist.Poisson: (_lp_poisson, ("rate",), False),
+    dist.Uniform: (_lp_uniform, ("low", "high"), True),
+    dist.Beta: (_lp_beta, ("concentration1", "concentration0"), True),
+    dist.Pareto: (_lp_pareto, ("scale", "alpha"), True),
+    dist.BinomialProbs: (_lp_binomial_probs, ("total_count", "probs"), False),
+    dist.BinomialLogits: (_lp_binomial_logits, ("total_count", "logits"), False),
 }
+_BINOMIAL = (dist.BinomialProbs, dist.BinomialLogits)
+# support -> transform code of a latent site
+_SUPPORT_CODE = {"real": REAL, "positive": POSITIVE, "unit_interval": UNIT, "interval": UNIT, "greater_than": LOWER}
+
+
+def _site_bounds(base, name):
+    """(lo, width) float64 of a latent site's affine part, or None: the bounds are host constants."""
+    if isinstance(base, dist.Uniform):
+        bounds = (base.low, base.high)
+    elif isinstance(base, dist.Pareto):
+        bounds = (base.scale,)
+    else:
+        return None
+    for b in bounds:
+        if isinstance(b, Sym):
+            _refuse(name, f"a bound of {type(base).__name__} that depends on a latent site ({b!r}): bounds must be "
+                          "constants")
+    vals = [np.asarray(_host(b), np.float64) for b in bounds]
+    if any(v.ndim > 1 for v in vals):
+        _refuse(name, "a bound of rank > 1")
+    if len(vals) == 2:
+        if not np.all(vals[1] > vals[0]):
+            _refuse(name, "Uniform needs low < high")
+        return vals[0], vals[1] - vals[0]
+    return vals[0], np.float64(1.0)
 
 
 class _Refuse(NotImplementedError):
@@ -525,6 +608,8 @@ class _Lowering:
             return self.latents[x.args[0]]
         if op in ("neg", "exp", "log", "sqrt", "tanh", "log1p", "square"):
             return B.ew(op, self(x.args[0], site))
+        if op == "expit":  # exp(-softplus(-x)): log(expit(x)) then folds to -softplus(-x)
+            return B.ew("exp", B.ew("neg", B.ew("softplus", B.ew("neg", self(x.args[0], site)))))
         if op in _BINARY:
             return B.ew(op, self(x.args[0], site), self(x.args[1], site))
         if op == "sum":
@@ -550,7 +635,7 @@ class _Lowering:
                 _refuse(site, f"matmul of shapes {np.shape(_host(a)) if not isinstance(a, Sym) else a.shape} and "
                               f"{np.shape(_host(b)) if not isinstance(b, Sym) else b.shape}")
             return B.matvec(M, vec)
-        _refuse(site, f"operation {op!r} is not supported (supported: {sorted(_UNARY[:7] + _BINARY)}, sum, "
+        _refuse(site, f"operation {op!r} is not supported (supported: {sorted(_UNARY[:7] + _BINARY)}, expit, sum, "
                       "getitem, matmul)")
 
 
@@ -564,7 +649,7 @@ def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
     lat = sorted((s for s in trace.sites.values() if s.obs is None), key=lambda s: s.name)
     if not lat:
         raise _Refuse("program compiler: the model has no latent sample sites")
-    sites, offsets, o = [], {}, 0
+    sites, offsets, affine, o = [], {}, {}, 0
     for s in lat:
         base = _base(s.fn)
         if len(s.shape) > 1:
@@ -572,18 +657,40 @@ def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
         entry = _LOGPROB.get(type(base))
         if entry is None or not entry[2]:
             _refuse(s.name, f"{type(base).__name__} is not supported as a latent site")
-        if base.support not in ("real", "positive"):
-            _refuse(s.name, f"support {base.support!r} is not supported (real and positive are)")
+        if base.support not in _SUPPORT_CODE:
+            _refuse(s.name, f"support {base.support!r} is not supported ({', '.join(_SUPPORT_CODE)} are)")
         n = int(np.prod(s.shape, dtype=np.int64))
         if n <= 0:
             _refuse(s.name, "empty site")
-        sites.append((s.name, tuple(s.shape), POSITIVE if base.support == "positive" else REAL))
+        bounds = _site_bounds(base, s.name)
+        if bounds is not None:
+            if any(b.size not in (1, n) for b in bounds):
+                _refuse(s.name, f"bounds of {[b.size for b in bounds]} elements at a site of {n}")
+            affine[s.name] = bounds
+        sites.append((s.name, tuple(s.shape), _SUPPORT_CODE[base.support]))
         offsets[s.name] = (o, n)
         o += n
     B = _Builder(o)
     unconstrained = {name: _V(B, n, slot=off) for name, (off, n) in offsets.items()}
-    constrained = {name: (B.ew("exp", unconstrained[name]) if tr == POSITIVE else unconstrained[name])
-                   for name, _, tr in sites}
+    # per site: the constrained value, log x where the transform gives it (None otherwise) and
+    # the terms of log|J|
+    constrained, log_value, log_jac = {}, {}, {}
+    for name, _, tr in sites:
+        u = unconstrained[name]
+        lo, width = affine.get(name, (0.0, 1.0))
+        if tr == REAL:
+            constrained[name], log_value[name], log_jac[name] = u, None, []
+        elif tr == POSITIVE:  # ExpTransform: log|J| = u
+            constrained[name], log_value[name], log_jac[name] = B.ew("exp", u), u, [u]
+        elif tr == UNIT:  # sigmoid, in its stable forms: log x = -softplus(-u), log(1 - x) = -softplus(u)
+            logx, log1mx = -B.ew("softplus", -u), -B.ew("softplus", u)
+            x = B.ew("exp", logx)
+            B.log1m[x.slot] = log1mx
+            constrained[name] = B.ew("add", lo, B.ew("mul", width, x))
+            log_value[name] = logx if constrained[name] is x else None
+            log_jac[name] = [logx, log1mx, B.const(np.log(width))]
+        else:  # LOWER: x = lo + exp(u), log|J| = u
+            constrained[name], log_value[name], log_jac[name] = B.ew("add", lo, B.ew("exp", u)), None, [u]
     lower = _Lowering(B, constrained)
 
     const_total = 0.0
@@ -596,9 +703,11 @@ def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
         expand, pnames, _ = entry
         try:
             d = {p: lower(getattr(base, p), s.name) for p in pnames}
+            if isinstance(base, _BINOMIAL) and not d["total_count"].is_const:
+                _refuse(s.name, "a total_count that depends on a latent site: it must be data")
             if s.obs is None:
                 x = constrained[s.name]
-                logx = unconstrained[s.name] if base.support == "positive" else None
+                logx = log_value[s.name]
                 n_site = offsets[s.name][1]
             else:
                 xv = np.asarray(_host(s.obs), np.float64)
@@ -609,8 +718,8 @@ def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
                     logx = B.const(np.log(x.c)) if base.support == "positive" else None
                 n_site = max(int(np.prod(s.shape, dtype=np.int64)), x.n)
             terms = expand(B, d, x, logx)
-            if s.obs is None and base.support == "positive":
-                terms.append(unconstrained[s.name])  # ExpTransform log|J| = u
+            if s.obs is None:
+                terms += log_jac[s.name]
         except _Refuse:
             raise
         except NotImplementedError as e:
@@ -635,16 +744,17 @@ def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
         total = total + t
     u = B.ew("sub", B.const(-const_total), total)  # U = -log p; always the program's last op
     assert u.slot == B.next_slot - 1
-    pot = ProgramPotential(B.program(), sites, max_workspace_bytes)
+    pot = ProgramPotential(B.program(), sites, max_workspace_bytes, affine)
     return _with_traced_deterministics(pot, trace)
 
 
 class ProgramPotential(Potential):
     """A traced model's potential as a program (nmx_pe_program): one launch per evaluation."""
 
-    def __init__(self, program, sites, max_workspace_bytes=1 << 30):
+    def __init__(self, program, sites, max_workspace_bytes=1 << 30, affine=None):
         self.program = program
         self.sites = list(sites)
+        self.affine = dict(affine or {})  # name -> (lo, width) of the UNIT / LOWER sites with bounds
         self.dim = program.dim
         self.max_workspace_bytes = int(max_workspace_bytes)
         assert self.dim == sum(int(np.prod(s, dtype=np.int64)) for _, s, _ in self.sites)
