@@ -392,7 +392,8 @@ typedef struct nmx_program {
 } nmx_program;
 
 /* Validate a program whose arrays are in HOST memory: every opcode, count, stride, slot,
- * constant and index-pool reference and every gather index against the pool and slot sizes.
+ * constant and index-pool reference and every gather index against the pool and slot sizes;
+ * the two operands of one op may share z elements only as the same reference.
  * Needs no GPU.  NMX_ERR_INVALID with nmx_last_error naming the op otherwise; only a program
  * that passed may be uploaded and given to nmx_pe_program. */
 int nmx_program_check(const nmx_program* host_program);

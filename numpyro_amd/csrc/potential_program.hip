@@ -94,6 +94,11 @@ int nmx_program_check_impl(const nmx_program* hp, bool predictive, const int32_t
           return nmx_fail(NMX_ERR_INVALID, "op %d (%s): second operand %s %d (x%lld) out of range", k, nm,
                           b >= 0 ? "slot" : "constant", b >= 0 ? b : ~b, (long long)lb);
         if (a < 0 && b < 0) return nmx_fail(NMX_ERR_INVALID, "op %d (%s): both operands constant", k, nm);
+        // the adjoint of a z element has no fixed lane and the reverse op has no barrier between
+        // its two updates: two z operands may share elements only as the same reference
+        if (!predictive && a >= 0 && b >= 0 && a != b && a < p.dim && b < p.dim && a < b + lb && b < a + la)
+          return nmx_fail(NMX_ERR_INVALID, "op %d (%s): operands z[%d:%lld] and z[%d:%lld] overlap at different "
+                          "offsets", k, nm, a, (long long)(a + la), b, (long long)(b + lb));
       }
     } else if (op == NMX_OP_REDUCE_SUM) {
       if (!slot_ok(a, n)) return nmx_fail(NMX_ERR_INVALID, "op %d (%s): operand slot %d (x%d) out of range", k, nm, a, n);

@@ -108,6 +108,16 @@ class Program:
             self.consts = np.ascontiguousarray(self.consts64.astype(np.float32))
         self.index = np.ascontiguousarray(np.asarray(index, np.int32).reshape(-1))
         self.num_slots, self.dim = int(num_slots), int(dim)
+        # the host interpreters read M alone; the kernel's per-lane forward and wave-per-row reverse
+        # read the transposed copy behind it.  A pool whose halves disagree is refused once, here
+        # (a pool reference out of range is nmx_program_check's to name)
+        for k, (op, dst, a, b, n, sa, sb, aux) in enumerate(self.ops.tolist()):
+            if op == OPCODE["matvec"] and b < 0 and n > 0 and aux > 0 and ~b + 2 * n * aux <= self.consts64.size:
+                M = self.consts64[~b:~b + n * aux].reshape(n, aux)
+                Mt = self.consts64[~b + n * aux:~b + 2 * n * aux].reshape(aux, n)
+                if not np.array_equal(M.T, Mt, equal_nan=True):
+                    raise ValueError(f"op {k} (matvec): the second half of its constant pool is not the transpose "
+                                     f"of the {n} x {aux} matrix in the first half")
 
     @property
     def num_ops(self):

@@ -2,7 +2,8 @@
 into every kernel, SURVEY.md §5 "race detection / sanitizers") runs each schedule -- fused step
 with the covtype potential (full, tail and list forms), the launched wide step, the wide step
 fused with a D-split model, the persistent one-wave schedule, per-chain and pooled dense mass,
-the BNN -- in a subprocess (the library is loaded once per process) without a failed check."""
+the BNN -- in a subprocess (the library is loaded once per process) without a failed check.  The
+program kernels (k_program, k_program_predict) have a subprocess of their own."""
 import os
 import subprocess
 import sys
@@ -113,4 +114,50 @@ def test_persistent_lds_frontier_is_bitwise_the_arena_one():
     print(out[-2000:])
     assert r.returncode == 0, out[-3000:]
     assert "carry ok" in out
+    assert "NMX_DCHECK failed" not in out
+
+
+PROGRAM_SCRIPT = r"""
+import numpy as np, torch
+import predictive_cases as PC
+import program_op_cases as OC
+import program_zoo as Zoo
+from numpyro_amd import native
+from numpyro_amd.infer import MCMC, NUTS, Predictive
+from numpyro_amd.program import ProgramPotential
+from test_gpu_program import G_TOL, U_TOL, _launch
+assert native.LIB_PATH.endswith("libnumpyro_amd_debug.so"), native.LIB_PATH
+device = torch.device("cuda:0")
+for family, name in [("matvec", "z3.5x200"), ("matvec", "tanh.65x129"), ("gather", "random.z3.65from130"),
+                     ("fanout", "fanout.n70")]:
+    c = OC.case(family, name)
+    pe, g = _launch(c.pot, c.Z, device)
+    U, G = c.reference()
+    np.testing.assert_allclose(pe, U, err_msg=name, **U_TOL)
+    np.testing.assert_allclose(g, G, err_msg=name, **G_TOL)
+case = Zoo.CASES["poisson"]()
+m = MCMC(NUTS(case.model), num_warmup=20, num_samples=5, num_chains=32, progress_bar=False)
+m.run(1, *case.args, extra_fields=("num_steps",))
+assert isinstance(m.sampler._potential, ProgramPotential)
+assert int(m.get_extra_fields()["num_steps"].sum()) > 0
+out = Predictive(case.model, m.get_samples())(2, *PC.unobserved_args(case))
+assert out["y"].shape == (32 * 5, case.args[0].shape[0]) and int(out["y"].min()) >= 0
+torch.cuda.synchronize()
+print("program debug ok")
+"""
+
+
+def test_debug_build_runs_the_program_kernels_without_a_failed_check():
+    """k_program and k_program_predict in the debug build: the matvec on its wave-per-row and
+    per-lane branches, a gather, one value with four readers, NUTS on a compiled model and one
+    Predictive call, without a failed NMX_DCHECK."""
+    lib = os.path.join(ROOT, "numpyro_amd", "_lib", "libnumpyro_amd_debug.so")
+    if not os.path.exists(lib):
+        pytest.fail("debug library missing: run numpyro_amd.build(debug=True) (done by __graft_entry__.build())")
+    env = dict(os.environ, NUMPYRO_AMD_DEBUG="1", PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "tests")]))
+    r = subprocess.run([sys.executable, "-c", PROGRAM_SCRIPT], cwd=ROOT, env=env, capture_output=True, text=True,
+                       timeout=110)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0, out[-3000:]
+    assert "program debug ok" in out
     assert "NMX_DCHECK failed" not in out
