@@ -371,6 +371,17 @@ size_t nmx_pe_bnn_workspace_bytes(int Dx, int H, int num_chains);
  *     adjoint: b + 1 row starts into n positions of dst, grouped by source element.
  *   NMX_OP_MATVEC: dst[i] = sum_k M[i][k] a[k], i < n, k < aux; M [n][aux] row-major at
  *     constant offset ~b, followed by its transpose [aux][n].
+ *   NMX_OP_CUMSUM: dst[i] = sum_{j <= i} a[j], i < n; a is a slot value of n elements.  Each
+ *     chunk of 64 elements is an inclusive scan over the wave, the carry the last element of
+ *     the chunk before it; the adjoint g_a[j] += sum_{i >= j} g_dst[i] is the suffix scan,
+ *     chunks walked from the last one downwards.
+ *   NMX_OP_LOGSUMEXP: dst[i] = log sum_{k < aux} exp(a[i * aux + k]), i < n; a is a slot value
+ *     of n * aux elements, rows by columns, row-major (n = 1: the full reduction).  A row is
+ *     max + log sum exp(a - max), the max replaced by 0 when it is not finite: a row whose
+ *     maximum is -inf gives -inf and contributes 0 to the adjoint
+ *     g_a[e] += g_dst[e / aux] exp(a[e] - dst[e / aux]).
+ *   NMX_OP_CONCAT: dst[i] = a[i] for i < aux, b[i - aux] for aux <= i < n, 0 < aux < n; each
+ *     operand is a slot value or a constant (~ref), at least one a slot.
  * Sums run in an order fixed by the program alone (per-lane strided partial sums, then a
  * fixed butterfly over the 64 lanes), with no atomics: U and the gradient are bitwise
  * independent of chain count, position, ldc, list order. ---- */
@@ -379,6 +390,7 @@ enum nmx_opcode {
   NMX_OP_SOFTPLUS, NMX_OP_LGAMMA,                                       /* unary */
   NMX_OP_ADD, NMX_OP_SUB, NMX_OP_MUL, NMX_OP_DIV, NMX_OP_POW,           /* binary */
   NMX_OP_REDUCE_SUM, NMX_OP_GATHER, NMX_OP_MATVEC,
+  NMX_OP_CUMSUM, NMX_OP_LOGSUMEXP, NMX_OP_CONCAT,                       /* read across elements, like the row above */
   NMX_NUM_OPCODES
 };
 #define NMX_OP_WORDS 8
@@ -393,8 +405,8 @@ typedef struct nmx_program {
 
 /* Validate a program whose arrays are in HOST memory: every opcode, count, stride, slot,
  * constant and index-pool reference and every gather index against the pool and slot sizes;
- * the two operands of one op may share z elements only as the same reference.
- * Needs no GPU.  NMX_ERR_INVALID with nmx_last_error naming the op otherwise; only a program
+ * the two operands of one op (elementwise or concat) may share z elements only as the same
+ * reference.  Needs no GPU.  NMX_ERR_INVALID with nmx_last_error naming the op otherwise; only a program
  * that passed may be uploaded and given to nmx_pe_program. */
 int nmx_program_check(const nmx_program* host_program);
 /* Workspace of nmx_pe_program: values and adjoints of ldc positions. */

@@ -4,10 +4,12 @@
 //
 // Lane mapping: element i of every value is computed, and its adjoint accumulated, by lane
 // i % 64 (scalars by lane 0).  An op whose operands are read at the element it writes needs no
-// synchronisation; the ops that read across lanes (reduce, gather, matvec, a broadcast scalar
-// slot) are preceded by a workgroup barrier.  Every sum has an order fixed by the program:
+// synchronisation; the ops that read across lanes (reduce, gather, matvec, cumsum, logsumexp,
+// concat, a broadcast scalar slot) are preceded by a workgroup barrier, and every one of them
+// writes only elements its lane owns.  Every sum has an order fixed by the program:
 // a lane adds its elements i = lane, lane + 64, ... in order, the 64 partial sums are combined by
-// a butterfly (every lane ends with the same bits).  No atomics.
+// a butterfly (every lane ends with the same bits); a cumsum is a wave scan per chunk of 64 with
+// the carry of the chunk before.  No atomics.
 #pragma once
 #include <math.h>
 
@@ -108,7 +110,7 @@ struct NmxProgram {
     } else if (o.op == NMX_OP_GATHER) {
       const int32_t* idx = p.index + o.aux;
       for (int i = lane; i < o.n; i += 64) v[o.dst + i] = v[o.a + idx[i]];
-    } else {  // NMX_OP_MATVEC
+    } else if (o.op == NMX_OP_MATVEC) {
       const int K = o.aux;
       const float* M = p.consts + ~o.b;
       const float* Mt = M + (size_t)o.n * K;
@@ -126,8 +128,54 @@ struct NmxProgram {
           v[o.dst + i] = s;
         }
       }
+    } else if (__builtin_expect(o.op == NMX_OP_CUMSUM, 0)) {
+      // inclusive scan of each chunk of 64 over the wave; the carry is the chunk's last element
+      float carry = 0.0f;
+      for (int base = 0; base < o.n; base += 64) {
+        const int i = base + lane;
+        float x = i < o.n ? v[o.a + i] : 0.0f;
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+          const float y = __shfl_up(x, m, 64);
+          if (lane >= m) x += y;
+        }
+        x += carry;
+        if (i < o.n) v[o.dst + i] = x;
+        carry = __shfl(x, 63, 64);
+      }
+    } else if (__builtin_expect(o.op == NMX_OP_LOGSUMEXP, 0)) {
+      const int K = o.aux;
+      if (wave_per_row(o.n, K)) {
+        for (int i = 0; i < o.n; ++i) {
+          const float* row = v + o.a + (size_t)i * K;
+          float m = -INFINITY;
+          for (int k = lane; k < K; k += 64) m = fmaxf(m, row[k]);
+#pragma unroll
+          for (int w = 32; w >= 1; w >>= 1) m = fmaxf(m, __shfl_xor(m, w, 64));
+          m = lse_shift(m);
+          float s = 0.0f;
+          for (int k = lane; k < K; k += 64) s += expf(row[k] - m);
+          s = nmx_wave_sum(s);
+          if (lane == (i & 63)) v[o.dst + i] = logf(s) + m;
+        }
+      } else {
+        for (int i = lane; i < o.n; i += 64) {
+          const float* row = v + o.a + (size_t)i * K;
+          float m = -INFINITY;
+          for (int k = 0; k < K; ++k) m = fmaxf(m, row[k]);
+          m = lse_shift(m);
+          float s = 0.0f;
+          for (int k = 0; k < K; ++k) s += expf(row[k] - m);
+          v[o.dst + i] = logf(s) + m;
+        }
+      }
+    } else {  // NMX_OP_CONCAT
+      for (int i = lane; i < o.n; i += 64) v[o.dst + i] = i < o.aux ? operand(v, o.a, i) : operand(v, o.b, i - o.aux);
     }
   }
+  // the shift of a log-sum-exp row: its maximum, or 0 where that is not finite (a row of -inf is
+  // then log 0 = -inf, one with +inf is +inf, neither is inf - inf)
+  __device__ __forceinline__ static float lse_shift(float m) { return fabsf(m) < INFINITY ? m : 0.0f; }
 
   __device__ __forceinline__ void reverse(const NmxOp& o, const float* v, float* g, int lane) const {
     if (o.op < NMX_OP_REDUCE_SUM) {
@@ -168,7 +216,7 @@ struct NmxProgram {
         for (int t = start[j]; t < start[j + 1]; ++t) s += g[o.dst + who[t]];
         g[o.a + j] += s;
       }
-    } else {  // NMX_OP_MATVEC: g_a += M^T g_dst
+    } else if (o.op == NMX_OP_MATVEC) {  // g_a += M^T g_dst
       const int K = o.aux;
       const float* M = p.consts + ~o.b;
       const float* Mt = M + (size_t)o.n * K;
@@ -186,6 +234,35 @@ struct NmxProgram {
           g[o.a + k] += s;
         }
       }
+    } else if (__builtin_expect(o.op == NMX_OP_CUMSUM, 0)) {
+      // g_a[j] += sum_{i >= j} g_dst[i]: the suffix scan, from the last chunk downwards
+      float carry = 0.0f;
+      for (int base = (o.n - 1) & ~63; base >= 0; base -= 64) {
+        const int i = base + lane;
+        float x = i < o.n ? g[o.dst + i] : 0.0f;
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+          const float y = __shfl_down(x, m, 64);
+          if (lane + m < 64) x += y;
+        }
+        x += carry;
+        if (i < o.n) g[o.a + i] += x;
+        carry = __shfl(x, 0, 64);
+      }
+    } else if (__builtin_expect(o.op == NMX_OP_LOGSUMEXP, 0)) {
+      // by the owner of each flat element: reads its row's result and adjoint, writes its own
+      const int K = o.aux, total = o.n * K;
+      for (int e = lane; e < total; e += 64) {
+        const int i = e / K;
+        const float d = v[o.dst + i];
+        const float w = d == -INFINITY ? 0.0f : expf(v[o.a + e] - d);
+        g[o.a + e] += g[o.dst + i] * w;
+      }
+    } else {  // NMX_OP_CONCAT: each part by the owner of the operand's element
+      if (o.a >= 0)
+        for (int i = lane; i < o.aux; i += 64) g[o.a + i] += g[o.dst + i];
+      if (o.b >= 0)
+        for (int j = lane; j < o.n - o.aux; j += 64) g[o.b + j] += g[o.dst + o.aux + j];
     }
   }
 
@@ -196,7 +273,8 @@ struct NmxProgram {
   }
   // z slots are referenced at any offset: their adjoints have no fixed lane
   __device__ __forceinline__ bool touches_z(const NmxOp& o) const {
-    return (o.a >= 0 && o.a < p.dim) || (o.op >= NMX_OP_ADD && o.op < NMX_OP_REDUCE_SUM && o.b >= 0 && o.b < p.dim);
+    const bool b_is_operand = (o.op >= NMX_OP_ADD && o.op < NMX_OP_REDUCE_SUM) || o.op == NMX_OP_CONCAT;
+    return (o.a >= 0 && o.a < p.dim) || (b_is_operand && o.b >= 0 && o.b < p.dim);
   }
 
   // chain c at position pos of the batch; called by all 64 lanes of a one-wave workgroup

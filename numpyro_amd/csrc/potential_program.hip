@@ -21,7 +21,7 @@ __global__ __launch_bounds__(64) void k_program(NmxProgram prog, nmx_eval_batch 
 
 const char* const OP_NAMES[NMX_NUM_OPCODES] = {"neg", "exp", "log", "sqrt", "tanh", "log1p", "square", "softplus",
                                                "lgamma", "add", "sub", "mul", "div", "pow", "reduce_sum",
-                                               "gather", "matvec"};
+                                               "gather", "matvec", "cumsum", "logsumexp", "concat"};
 const char* const DRAW_NAMES[NMX_DRAW_END - NMX_DRAW_NORMAL] = {"draw_normal", "draw_exponential", "draw_cauchy",
                                                                 "draw_gamma", "draw_bernoulli", "draw_poisson",
                                                                 "draw_uniform", "draw_binomial"};
@@ -124,12 +124,35 @@ int nmx_program_check_impl(const nmx_program* hp, bool predictive, const int32_t
           if (who[t] < 0 || who[t] >= n || idx[who[t]] != j)
             return nmx_fail(NMX_ERR_INVALID, "op %d (%s): transposed index entry %d does not match the index", k, nm, t);
       }
-    } else {  // NMX_OP_MATVEC
+    } else if (op == NMX_OP_MATVEC) {
       if (aux <= 0 || !slot_ok(a, aux))
         return nmx_fail(NMX_ERR_INVALID, "op %d (%s): vector slot %d of length %d out of range", k, nm, a, aux);
       if (!const_ok(b, 2 * (int64_t)n * aux))
         return nmx_fail(NMX_ERR_INVALID, "op %d (%s): matrix constant %d (%d x %d and its transpose) outside the pool "
                         "of %d", k, nm, b < 0 ? ~b : b, n, aux, p.num_consts);
+    } else if (op == NMX_OP_CUMSUM) {
+      if (!slot_ok(a, n)) return nmx_fail(NMX_ERR_INVALID, "op %d (%s): operand slot %d (x%d) out of range", k, nm, a, n);
+    } else if (op == NMX_OP_LOGSUMEXP) {
+      if (aux < 1) return nmx_fail(NMX_ERR_INVALID, "op %d (%s): %d columns (aux) < 1", k, nm, aux);
+      const int64_t len = (int64_t)n * aux;  // a value of `len` slots fits the int32 slot count
+      if (!slot_ok(a, len))
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): operand slot %d of %d x %d = %lld elements out of range", k, nm, a,
+                        n, aux, (long long)len);
+    } else {  // NMX_OP_CONCAT
+      if (aux <= 0 || aux >= n)
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): first part of %d elements (aux) not inside (0, %d)", k, nm, aux, n);
+      const int64_t la = aux, lb = n - aux;
+      if (a >= 0 ? !slot_ok(a, la) : !const_ok(a, la))
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): first operand %s %d (x%lld) out of range", k, nm,
+                        a >= 0 ? "slot" : "constant", a >= 0 ? a : ~a, (long long)la);
+      if (b >= 0 ? !slot_ok(b, lb) : !const_ok(b, lb))
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): second operand %s %d (x%lld) out of range", k, nm,
+                        b >= 0 ? "slot" : "constant", b >= 0 ? b : ~b, (long long)lb);
+      if (a < 0 && b < 0) return nmx_fail(NMX_ERR_INVALID, "op %d (%s): both operands constant", k, nm);
+      // as for the elementwise ops: the reverse op has no barrier between its two updates
+      if (!predictive && a >= 0 && b >= 0 && a != b && a < p.dim && b < p.dim && a < b + lb && b < a + la)
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): operands z[%d:%lld] and z[%d:%lld] overlap at different "
+                        "offsets", k, nm, a, (long long)(a + la), b, (long long)(b + lb));
     }
     def_len[dst] = (int32_t)dst_len;
     cursor += dst_len;

@@ -12,7 +12,11 @@
 
 namespace {
 
-__global__ __launch_bounds__(64) void k_program_predict(NmxPredict pr, const float* __restrict__ samples,
+// 6 waves / SIMD is the kernel's occupancy since the binomial draw (80 VGPRs, nmx_program.h
+// nmx_draw_binomial).  The cumsum / logsumexp / concat cases of NmxProgram::forward made the
+// allocator take 87 VGPRs (5 waves) although no path needs more than 80; with the occupancy
+// stated it allocates 80 again, without a spill or scratch (DESIGN.md "Simplex latents").
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6))) void k_program_predict(NmxPredict pr, const float* __restrict__ samples,
                                                         int num_samples, uint32_t sample_offset,
                                                         float* __restrict__ tape) {
   const int row = blockIdx.x;

@@ -9,7 +9,9 @@ Normal (continuous.py:2171), HalfCauchy (:700), Exponential (:455), Gamma (:490)
 (:2344), Bernoulli / BernoulliLogits (discrete.py:108-139), GaussianRandomWalk (continuous.py:
 658), MultivariateNormal (:1487), HalfNormal (:829), LogNormal (:1166), Cauchy (:217), Poisson
 (discrete.py:748; observed sites only), Uniform (continuous.py:2431), Beta (:165), Pareto (:2230),
-BinomialProbs / BinomialLogits / Binomial (discrete.py:172, :243, :298; observed sites only);
+BinomialProbs / BinomialLogits / Binomial (discrete.py:172, :243, :298; observed sites only),
+Dirichlet (continuous.py), CategoricalProbs / CategoricalLogits / Categorical (discrete.py) and
+MixtureSameFamily (mixtures.py), the last two kinds as observed sites only;
 ``.to_event`` / ``.expand`` (distribution.py:377-420).
 """
 from __future__ import annotations
@@ -263,6 +265,80 @@ def Binomial(total_count=1, probs=None, logits=None):
     if (probs is None) == (logits is None):
         raise ValueError("One of `probs` or `logits` must be specified.")
     return BinomialLogits(logits, total_count) if logits is not None else BinomialProbs(probs, total_count)
+
+
+class Dirichlet(Distribution):
+    """numpyro/distributions/continuous.py Dirichlet: event shape (K,), support the simplex.  The
+    program compiler takes a concentration of rank 1 (constant or symbolic)."""
+
+    support = "simplex"
+
+    def __init__(self, concentration):
+        shape = shape_of(concentration)
+        if len(shape) < 1:
+            raise ValueError("`concentration` parameter must be at least one-dimensional.")
+        super().__init__(shape[:-1], shape[-1:])
+        self.concentration = concentration
+
+    def params(self):
+        return {"concentration": self.concentration}
+
+
+class CategoricalProbs(Distribution):
+    """Observed sites only (a discrete latent cannot be sampled by HMC).  The last axis of
+    ``probs`` is the category axis (discrete.py CategoricalProbs)."""
+
+    support = "integer_interval"
+
+    def __init__(self, probs):
+        shape = shape_of(probs)
+        if len(shape) < 1:
+            raise ValueError("`probs` parameter must be at least one-dimensional.")
+        super().__init__(shape[:-1])
+        self.probs = probs
+
+    def params(self):
+        return {"probs": self.probs}
+
+
+class CategoricalLogits(Distribution):
+    """Observed sites only; the last axis of ``logits`` is the category axis."""
+
+    support = "integer_interval"
+
+    def __init__(self, logits):
+        shape = shape_of(logits)
+        if len(shape) < 1:
+            raise ValueError("`logits` parameter must be at least one-dimensional.")
+        super().__init__(shape[:-1])
+        self.logits = logits
+
+    def params(self):
+        return {"logits": self.logits}
+
+
+def Categorical(probs=None, logits=None):
+    """numpyro/distributions/discrete.py Categorical: dispatch on probs / logits."""
+    if (probs is None) == (logits is None):
+        raise ValueError("One of `probs` or `logits` must be specified.")
+    return CategoricalLogits(logits) if logits is not None else CategoricalProbs(probs)
+
+
+class MixtureSameFamily(Distribution):
+    """numpyro/distributions/mixtures.py MixtureSameFamily: the component distribution's last
+    batch axis is the mixture axis.  Observed sites only: the program compiler marginalises the
+    component index (log-sum-exp over the components)."""
+
+    def __init__(self, mixing_distribution, component_distribution):
+        cb = tuple(component_distribution.batch_shape)
+        super().__init__(cb[:-1], component_distribution.event_shape)
+        self.mixing_distribution = mixing_distribution
+        self.component_distribution = component_distribution
+        self.support = component_distribution.support
+
+    def params(self):
+        return {"mixing_distribution": self.mixing_distribution,
+                "component_distribution": self.component_distribution}
 
 
 class GaussianRandomWalk(Distribution):

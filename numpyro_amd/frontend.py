@@ -16,7 +16,7 @@ the model to the program compiler (numpyro_amd/program.py compile_model), which 
 traced log-joint to a straight-line program of primitive operations evaluated, with its
 reverse-mode adjoint, by one HIP kernel (csrc/potential_program.hip).  A model that matches a
 fused kernel always gets it; a model outside the program compiler's class (rank-2 latents,
-simplex supports, reparam configs, operations outside numpyro_amd.jnp) is refused by both.
+batched simplex sites, reparam configs, operations outside numpyro_amd.jnp) is refused by both.
 """
 from __future__ import annotations
 
@@ -319,7 +319,7 @@ def potential_from_model(model, args=(), kwargs=None):
 # ----------------------------------------------------------------------------- deterministic sites
 _SYM_UNARY = {"tanh": "tanh", "exp": "exp", "sqrt": "sqrt", "log": "log", "neg": "neg", "log1p": "log1p",
               "square": "square", "expit": "sigmoid"}
-_SYM_OTHER = ("matmul", "sum", "getitem")
+_SYM_OTHER = ("matmul", "sum", "getitem", "cumsum", "logsumexp", "concatenate")
 _SYM_BINARY = {"add": "add", "sub": "sub", "mul": "mul", "div": "div", "pow": "pow"}
 
 
@@ -349,6 +349,15 @@ def eval_sym(x, values):
     if x.op == "sum":  # full reduction of a vector (the event dimension)
         v = eval_sym(x.args[0], values)
         return v.sum(-1) if len(shape_of(x.args[0])) else v
+    if x.op == "cumsum":
+        return torch.cumsum(eval_sym(x.args[0], values), -1)
+    if x.op == "logsumexp":
+        v = eval_sym(x.args[0], values)
+        return torch.logsumexp(v, -1) if len(shape_of(x.args[0])) else v
+    if x.op == "concatenate":  # vectors: constants take the batch dimensions of the symbolic parts
+        parts = [eval_sym(a, values) for a in x.args]
+        batch = next(tuple(v.shape[:-1]) for a, v in zip(x.args, parts) if isinstance(a, Sym))
+        return torch.cat([v.expand(*batch, v.shape[-1]) for v in parts], -1)
     if x.op == "getitem":  # leading event axis of a vector: the last dimension of the batch of draws
         v, idx = eval_sym(x.args[0], values), x.args[1]
         if not isinstance(idx, (int, slice)):
@@ -393,7 +402,7 @@ def _with_traced_deterministics(pot, trace):
     for name, expr in dets.items():  # unsupported operations fail here, not after sampling
         _check_sym(expr, name)
     base = pot.deterministic
-    site_shape = {n: tuple(s) for n, s, _ in pot.sites}
+    site_shape = pot.constrained_shapes()  # the values a deterministic site sees are constrained
 
     def deterministic(sites):
         import torch

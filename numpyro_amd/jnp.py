@@ -1,8 +1,11 @@
 """The array functions the reference's example models call on jax.numpy (matmul, dot, tanh,
-exp, log, log1p, sqrt, square, expit, sum, zeros, ones, shape; indexing a vector), working on NumPy / torch arrays and on the symbolic values of
+exp, log, log1p, sqrt, square, expit, sum, cumsum, logsumexp (jax.scipy.special's), concatenate,
+zeros, ones, shape; indexing a vector), working on NumPy / torch arrays and on the symbolic values of
 latent sites while the model front end traces a model (numpyro_amd/frontend.py).  Write
 ``from numpyro_amd import jnp`` where a numpyro model has ``import jax.numpy as jnp``."""
 from __future__ import annotations
+
+import builtins
 
 import numpy as np
 
@@ -106,6 +109,44 @@ def sum(x, axis=None):  # noqa: A001  (jax.numpy's name)
             raise NotImplementedError("jnp.sum of a symbolic value is the full reduction of a vector")
         return Sym("sum", (x,), ())
     return np.sum(np.asarray(x) if not hasattr(x, "cpu") else x.cpu().numpy(), axis=axis)
+
+
+def _np(x):
+    return np.asarray(x) if not hasattr(x, "cpu") else x.cpu().numpy()
+
+
+def cumsum(x, axis=None):
+    """Cumulative sum of a value of rank <= 1."""
+    if isinstance(x, Sym):
+        if len(x.shape) != 1 or axis not in (None, 0, -1):
+            raise NotImplementedError("jnp.cumsum of a symbolic value is the cumulative sum of a vector")
+        return Sym("cumsum", (x,), x.shape)
+    return np.cumsum(_np(x), axis=axis)
+
+
+def logsumexp(x, axis=None):
+    """jax.scipy.special.logsumexp: the full reduction of a value of rank <= 1 (a row of -inf
+    gives -inf)."""
+    if isinstance(x, Sym):
+        if len(x.shape) > 1 or axis not in (None, 0, -1):
+            raise NotImplementedError("logsumexp of a symbolic value is the full reduction of a vector")
+        return Sym("logsumexp", (x,), ())
+    a = np.asarray(_np(x), np.float64)
+    with np.errstate(all="ignore"):
+        m = np.max(a, axis=axis, keepdims=True)
+        m = np.where(np.isfinite(m), m, 0.0)
+        return np.log(np.sum(np.exp(a - m), axis=axis)) + (m.reshape(()) if axis is None else np.squeeze(m, axis))
+
+
+def concatenate(arrays, axis=0):
+    """Concatenation of vectors (constants or symbolic values of rank 1)."""
+    arrays = list(arrays)
+    if builtins.any(isinstance(a, Sym) for a in arrays):
+        shapes = [shape_of(a) for a in arrays]
+        if builtins.any(len(s) != 1 for s in shapes) or axis not in (0, -1):
+            raise NotImplementedError("jnp.concatenate with a symbolic value joins vectors (rank 1) on axis 0")
+        return Sym("concatenate", arrays, (builtins.sum(s[0] for s in shapes),))
+    return np.concatenate([_np(a) for a in arrays], axis=axis)
 
 
 def matmul(a, b):

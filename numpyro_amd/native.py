@@ -108,7 +108,7 @@ class EvalBatch(ctypes.Structure):
 
 # enum nmx_opcode (order matters): unary, binary, then the ops that read across elements
 OPCODES = ["neg", "exp", "log", "sqrt", "tanh", "log1p", "square", "softplus", "lgamma",
-           "add", "sub", "mul", "div", "pow", "reduce_sum", "gather", "matvec"]
+           "add", "sub", "mul", "div", "pow", "reduce_sum", "gather", "matvec", "cumsum", "logsumexp", "concat"]
 OPCODE = {n: i for i, n in enumerate(OPCODES)}
 OP_WORDS = 8  # NMX_OP_WORDS: opcode, dst, a, b, n, sa, sb, aux
 

@@ -28,6 +28,21 @@ REAL, POSITIVE = 0, 1  # transform codes: identity, ExpTransform (transforms.py:
 # (``Potential.affine``).  The step kernels collect coordinates of these codes unconstrained;
 # ``Potential.constrain`` completes the transform in torch.
 UNIT, LOWER = 2, 3
+# the simplex by stick breaking (StickBreakingTransform, transforms.py): a site of event shape
+# (K,) has K - 1 unconstrained coordinates, and ``sites`` carries that shape (K - 1,); u = 0 is
+# the uniform point.  Collected unconstrained like UNIT and LOWER.
+SIMPLEX = 4
+
+
+def stick_breaking(u):
+    """[..., K - 1] unconstrained -> [..., K] on the simplex, in log space as the program compiler
+    builds it (program.py compile_model): t = u - log(K - 1 - k), log z = -softplus(-t),
+    log(1 - z) = -softplus(t), log x = (log z, 0) + (0, cumsum log(1 - z))."""
+    m = u.shape[-1]
+    t = u - torch.log(torch.arange(m, 0, -1, dtype=u.dtype, device=u.device))
+    zero = torch.zeros_like(u[..., :1])
+    log_z, log_1mz = -torch.logaddexp(-t, zero), -torch.logaddexp(t, zero)  # softplus without a cut
+    return torch.exp(torch.cat([log_z, zero], -1) + torch.cat([zero, torch.cumsum(log_1mz, -1)], -1))
 
 
 class Potential:
@@ -94,11 +109,19 @@ class Potential:
                 v = torch.sigmoid(v)  # the stable form: exp is only taken of -|u|
             elif tr == LOWER:
                 v = torch.exp(v)
-            if tr >= UNIT and name in self.affine:
+            elif tr == SIMPLEX:
+                v = stick_breaking(v)
+            if tr in (UNIT, LOWER) and name in self.affine:
                 lo, width = (torch.as_tensor(np.asarray(b), dtype=v.dtype, device=v.device) for b in self.affine[name])
                 v = lo + width * v
             out[name] = v
         return out
+
+    def constrained_shapes(self):
+        """{site: shape of its constrained value}: ``sites`` holds the unconstrained shapes, which
+        differ for a SIMPLEX site ((K - 1,) unconstrained, (K,) constrained)."""
+        return {name: tuple(shape[:-1]) + (shape[-1] + 1,) if tr == SIMPLEX else tuple(shape)
+                for name, shape, tr in self.sites}
 
     def unflatten(self, flat):
         """[..., D] -> {site: [..., *shape]} (ravel_pytree order)."""

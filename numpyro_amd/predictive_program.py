@@ -30,7 +30,8 @@ from . import distributions as dist
 from . import native
 from .frontend import _base, _host, trace_model
 from .jnp import Sym, shape_of
-from .program import _BINARY, _HOST_FWD, _LOGPROB, _UNARY, Program, _Builder, _Lowering, _Refuse, _refuse, _V
+from .program import (_BINARY, _HOST_FWD, _LOGPROB, _SCAN, _UNARY, Program, _Builder, _Lowering, _Refuse,
+                      _host_scan_fwd, _refuse, _V)
 
 _DRAW_NAME = {v: k for k, v in native.DRAW_OPCODE.items()}
 _U24 = 5.9604644775390625e-08  # 2^-24
@@ -118,6 +119,17 @@ def _dr_binomial_logits(B, d, n):
     return B.draw("draw_binomial", n, _binomial_count(d), 1.0 / (1.0 + B.ew("exp", -d["logits"])))
 
 
+def _dr_dirichlet(B, d, n):
+    # normalised gamma draws; where every draw underflows to 0 (concentrations far below 1) this is
+    # 0 / 0 = NaN, as _dr_beta
+    a = d["concentration"]
+    if a.n != n or n < 2:
+        raise NotImplementedError(f"a Dirichlet of {n} components with a concentration of {a.n} elements (supported: "
+                                  "one vector of K >= 2 components)")
+    g = B.draw("draw_gamma", n, a)
+    return g / B.rsum(g)
+
+
 _DRAW = {
     dist.Normal: _dr_normal, dist.StudentT: _dr_student_t, dist.Cauchy: _dr_cauchy,
     dist.HalfCauchy: _dr_half_cauchy, dist.HalfNormal: _dr_half_normal, dist.LogNormal: _dr_log_normal,
@@ -125,9 +137,14 @@ _DRAW = {
     dist.BernoulliProbs: _dr_bernoulli_probs, dist.Poisson: _dr_poisson,
     dist.Uniform: _dr_uniform, dist.Beta: _dr_beta, dist.Pareto: _dr_pareto,
     dist.BinomialProbs: _dr_binomial_probs, dist.BinomialLogits: _dr_binomial_logits,
+    dist.Dirichlet: _dr_dirichlet,
 }
-assert set(_DRAW) == set(_LOGPROB)
-_INTEGER = (dist.BernoulliLogits, dist.BernoulliProbs, dist.Poisson, dist.BinomialProbs, dist.BinomialLogits)
+# drawing one of these needs an index that depends on a draw (the category, the component): the
+# program has no such op, so they are supported with data only
+_UNDRAWABLE = (dist.CategoricalProbs, dist.CategoricalLogits, dist.MixtureSameFamily)
+assert set(_DRAW) | set(_UNDRAWABLE) == set(_LOGPROB) and not set(_DRAW) & set(_UNDRAWABLE)
+_INTEGER = (dist.BernoulliLogits, dist.BernoulliProbs, dist.Poisson, dist.BinomialProbs, dist.BinomialLogits,
+            dist.CategoricalProbs, dist.CategoricalLogits)
 
 
 class Output:
@@ -242,6 +259,8 @@ class PredictiveProgram(Program):
                 elif nm == "matvec":
                     M = cp[~b:~b + n * aux].reshape(n, aux)
                     v[:, dst:dst + n] = v[:, a:a + aux] @ M.T
+                elif nm in _SCAN:
+                    _host_scan_fwd(nm, v, cp, dst, a, b, n, aux)
                 else:
                     par = None if nm in _NO_PARAM else np.broadcast_to(operand(a, n, sa), (S, n))
                     if nm == "draw_binomial":
@@ -485,8 +504,11 @@ def compile_predictive(model, args=(), kwargs=None, given=()):
     sizes = {}
     for s in trace.sites.values():
         base = _base(s.fn)
-        if type(base) not in _DRAW:
+        if type(base) not in _LOGPROB:
             _refuse(s.name, f"{type(base).__name__} is not supported")
+        if type(base) in _UNDRAWABLE and s.obs is None and s.name not in given:
+            _refuse(s.name, f"drawing a {type(base).__name__} site needs a data-dependent index, which predictive "
+                            "programs do not have: pass its data, or leave the site out of the model")
         if len(s.shape) > 1:
             _refuse(s.name, f"site of shape {s.shape}: sites of rank > 1 are not supported")
         if s.obs is not None and np.ndim(_host(s.obs)) > 1:

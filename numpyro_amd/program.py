@@ -21,10 +21,14 @@ Model class: latent sites of rank 0 or 1 with support ``real``, ``positive`` (th
 sees u = log x and the program adds -sum(u), as NmxEightSchools does), ``unit_interval`` /
 ``interval`` (x = lo + width sigmoid(u), built from -softplus(-u) and -softplus(u)) or
 ``greater_than`` (x = lo + exp(u)), with constant bounds, from Normal, StudentT, Cauchy,
-HalfCauchy, HalfNormal, LogNormal, Exponential, Gamma, Uniform, Beta, Pareto; observed sites from
-those plus BernoulliLogits / BernoulliProbs / Poisson / BinomialLogits / BinomialProbs (with a
-total_count that is data); parameters that are constants or expressions of latents over
-numpyro_amd.jnp's operations.  Anything else raises NotImplementedError naming the site.
+HalfCauchy, HalfNormal, LogNormal, Exponential, Gamma, Uniform, Beta, Pareto, and one Dirichlet
+vector per site (``simplex``: K - 1 unconstrained coordinates, stick breaking built in log space
+from the cumsum and concat ops); observed sites from those plus BernoulliLogits / BernoulliProbs /
+Poisson / BinomialLogits / BinomialProbs (with a total_count that is data), CategoricalProbs /
+CategoricalLogits (a parameter of rank 1) and MixtureSameFamily of a Categorical with univariate
+continuous components (the N x K table through a row-wise logsumexp); parameters that are
+constants or expressions of latents over numpyro_amd.jnp's operations.  Anything else raises
+NotImplementedError naming the site.
 """
 from __future__ import annotations
 
@@ -38,7 +42,7 @@ from . import native
 from .frontend import _base, _host, _with_traced_deterministics, trace_model
 from .jnp import Sym
 from .native import OPCODE
-from .potentials import LOWER, POSITIVE, REAL, UNIT, Potential
+from .potentials import LOWER, POSITIVE, REAL, SIMPLEX, UNIT, Potential
 
 _UNARY = ("neg", "exp", "log", "sqrt", "tanh", "log1p", "square", "softplus", "lgamma")
 _BINARY = ("add", "sub", "mul", "div", "pow")
@@ -93,6 +97,46 @@ def _host_rev(op, gd, x, y, out):
     if op == "div":
         return gd / y, -(gd * out) / y
     return gd * (y * np.power(x, y - 1.0)), gd * (out * np.log(x))  # pow
+
+
+def _host_logsumexp(x):
+    """Row-wise over the last axis, as the kernel: max + log sum exp(x - max), the max replaced by
+    0 where it is not finite (jax.scipy.special.logsumexp's rule: a row of -inf gives -inf)."""
+    m = x.max(-1)
+    m = np.where(np.isfinite(m), m, x.dtype.type(0.0))
+    return np.log(np.exp(x - m[..., None]).sum(-1)) + m
+
+
+def _host_scan_fwd(nm, v, cp, dst, a, b, n, aux):
+    """Forward of cumsum / logsumexp / concat on the value table v [C, S] (any float dtype)."""
+    C = v.shape[0]
+    if nm == "cumsum":
+        v[:, dst:dst + n] = np.cumsum(v[:, a:a + n], 1)
+    elif nm == "logsumexp":
+        v[:, dst:dst + n] = _host_logsumexp(v[:, a:a + n * aux].reshape(C, n, aux))
+    else:  # concat
+        v[:, dst:dst + aux] = v[:, a:a + aux] if a >= 0 else cp[None, ~a:~a + aux]
+        v[:, dst + aux:dst + n] = v[:, b:b + n - aux] if b >= 0 else cp[None, ~b:~b + n - aux]
+
+
+def _host_scan_rev(nm, v, g, dst, a, b, n, aux):
+    """Reverse of cumsum / logsumexp / concat: the operands' adjoints in g [C, S]."""
+    C = v.shape[0]
+    gd = g[:, dst:dst + n]
+    if nm == "cumsum":  # the suffix sums
+        g[:, a:a + n] += np.cumsum(gd[:, ::-1], 1)[:, ::-1]
+    elif nm == "logsumexp":
+        x, out = v[:, a:a + n * aux].reshape(C, n, aux), v[:, dst:dst + n]
+        w = np.where(out[..., None] == -np.inf, x.dtype.type(0.0), np.exp(x - out[..., None]))
+        g[:, a:a + n * aux] += (gd[..., None] * w).reshape(C, n * aux)
+    else:
+        if a >= 0:
+            g[:, a:a + aux] += gd[:, :aux]
+        if b >= 0:
+            g[:, b:b + n - aux] += gd[:, aux:]
+
+
+_SCAN = ("cumsum", "logsumexp", "concat")
 
 
 class Program:
@@ -175,9 +219,11 @@ class Program:
                     v[:, dst] = v[:, a:a + n].sum(1)
                 elif nm == "gather":
                     v[:, dst:dst + n] = v[:, a + ix[aux:aux + n]]
-                else:  # matvec
+                elif nm == "matvec":
                     M = cp[~b:~b + n * aux].reshape(n, aux)
                     v[:, dst:dst + n] = v[:, a:a + aux] @ M.T
+                else:
+                    _host_scan_fwd(nm, v, cp, dst, a, b, n, aux)
             g[:, S - 1] = 1.0
             for op, dst, a, b, n, sa, sb, aux in reversed(ops):
                 nm = names[op]
@@ -198,9 +244,11 @@ class Program:
                     g[:, a:a + n] += gd
                 elif nm == "gather":
                     np.add.at(g, (slice(None), a + ix[aux:aux + n]), gd)
-                else:
+                elif nm == "matvec":
                     M = cp[~b:~b + n * aux].reshape(n, aux)
                     g[:, a:a + aux] += gd @ M
+                else:
+                    _host_scan_rev(nm, v, g, dst, a, b, n, aux)
         return v[:, S - 1].copy(), g[:, :D].copy()
 
     # ------------------------------------------------------------------ cost model
@@ -209,7 +257,12 @@ class Program:
         f = 0.0
         for op, dst, a, b, n, sa, sb, aux in self.ops.tolist():
             nm = native.OPCODES[op]
-            f += 4.0 * n * aux if nm == "matvec" else 2.0 * n if nm in ("reduce_sum", "gather") else 4.0 * n
+            if nm == "logsumexp":  # per element: max, subtract, exp, add; and subtract, exp, multiply, add
+                f += 8.0 * n * aux
+            elif nm == "concat":  # moves only
+                continue
+            else:
+                f += 4.0 * n * aux if nm == "matvec" else 2.0 * n if nm in ("reduce_sum", "gather", "cumsum") else 4.0 * n
         return f * num_chains
 
     def bytes_per_eval(self):
@@ -224,8 +277,12 @@ class Program:
                 src = [aux]
             elif nm == "gather":
                 src = [n]
-            elif nm == "reduce_sum":
+            elif nm in ("reduce_sum", "cumsum"):
                 src = [n]
+            elif nm == "logsumexp":
+                src = [n * aux]
+            elif nm == "concat":
+                src = [ln for r, ln in ((a, aux), (b, n - aux)) if r >= 0]
             else:
                 src = [(n if s else 1) for r, s in ((a, sa), (b, sb) if nm in _BINARY else (-1, 0)) if r >= 0]
             nd = 1 if nm == "reduce_sum" else n
@@ -374,6 +431,32 @@ class _Builder:
         off = self._pool(np.concatenate([M.reshape(-1), M.T.reshape(-1)]))
         return self._emit("matvec", M.shape[0], a.slot, ~off, M.shape[0], 1, 0, M.shape[1], ("matvec", a.slot, off))
 
+    def cumsum(self, a):
+        a = self.const(a)
+        if a.is_const:
+            return self.const(np.cumsum(a.c))
+        if a.n == 1:
+            return a
+        return self._emit("cumsum", a.n, a.slot, 0, a.n, 1, 0, 0, ("cumsum", a.slot, a.n))
+
+    def logsumexp(self, a, rows, cols):
+        """Row-wise over the flat row-major rows x cols value a: `rows` elements."""
+        a = self.const(a)
+        assert a.n == rows * cols and cols >= 1, (a.n, rows, cols)
+        if a.is_const:
+            with np.errstate(all="ignore"):
+                return self.const(_host_logsumexp(a.c.reshape(rows, cols)))
+        if cols == 1:
+            return a
+        return self._emit("logsumexp", rows, a.slot, 0, rows, 1, 0, cols, ("logsumexp", a.slot, rows, cols))
+
+    def concat(self, a, b):
+        a, b = self.const(a), self.const(b)
+        if a.is_const and b.is_const:
+            return self.const(np.concatenate([a.c, b.c]))
+        ra, rb, n = self._ref(a), self._ref(b), a.n + b.n
+        return self._emit("concat", n, ra, rb, n, 1, 1, a.n, ("concat", ra, rb, a.n, b.n))
+
     def unary(self, name):
         return lambda x: self.ew(name, x)
 
@@ -412,7 +495,7 @@ class _Builder:
                 if o[0] == draws["draw_binomial"]:
                     return (2, 3)
                 return (2,) if o[0] >= draws["draw_gamma"] and o[0] != draws["draw_uniform"] else ()
-            return (2, 3) if o[0] in binary else (2,)
+            return (2, 3) if o[0] in binary or o[0] == OPCODE["concat"] else (2,)
 
         def slot_refs(o):
             return [o[f] for f in fields(o) if o[f] >= dim]
@@ -534,6 +617,74 @@ def _lp_binomial_logits(B, d, x, logx):
     return [x * d["logits"], -(n * B.ew("softplus", d["logits"])), _binomial_coefficient(B, n, x)]
 
 
+# ---- distributions over a whole vector: their expansions return the terms of the site's total
+# log density (scalars), not elementwise terms
+def _lp_dirichlet(B, d, x, logx):
+    a = d["concentration"]
+    if a.n < 2:
+        raise NotImplementedError("a Dirichlet of fewer than 2 components")
+    if x.n != a.n:
+        raise NotImplementedError(f"a value of {x.n} elements under a concentration of {a.n}")
+    logx = B.ew("log", x) if logx is None else logx
+    return [B.rsum((a - 1.0) * logx), B.ew("lgamma", B.rsum(a)), -B.rsum(B.ew("lgamma", a))]
+
+
+def _category_index(x, K):
+    idx = np.asarray(x.c)
+    if K < 2:
+        raise NotImplementedError("a Categorical of fewer than 2 categories")
+    if not np.all(np.isfinite(idx)) or np.any(idx != np.floor(idx)) or np.any(idx < 0) or np.any(idx >= K):
+        raise NotImplementedError(f"observations that are not integers in [0, {K})")
+    return idx.astype(np.int64)
+
+
+def _lp_categorical_probs(B, d, x, logx):
+    p = d["probs"]
+    return [B.rsum(B.gather(B.ew("log", p), _category_index(x, p.n)))]
+
+
+def _lp_categorical_logits(B, d, x, logx):
+    lg = d["logits"]
+    idx = _category_index(x, lg.n)
+    return [B.rsum(B.gather(lg, idx)), -(float(idx.size) * B.logsumexp(lg, 1, lg.n))]
+
+
+_CATEGORICAL = (dist.CategoricalProbs, dist.CategoricalLogits)
+
+
+def _lp_mixture(B, lower, base, xv, site):
+    """MixtureSameFamily at observations xv [N]: the N x K table of component log densities plus
+    log weights, flat and row-major, through logsumexp(rows = N, cols = K), then summed."""
+    mixing, comp = _base(base.mixing_distribution), _base(base.component_distribution)
+    if not isinstance(mixing, _CATEGORICAL):
+        _refuse(site, f"a mixing distribution {type(mixing).__name__} (a Categorical is supported)")
+    entry = _LOGPROB.get(type(comp))
+    if entry is None or not entry[2] or isinstance(comp, _VECTOR) or comp.event_shape:
+        _refuse(site, f"a mixture of {type(comp).__name__} components (supported: the univariate continuous "
+                      "distributions)")
+    w = lower(mixing.probs if isinstance(mixing, dist.CategoricalProbs) else mixing.logits, site)
+    K, N = w.n, xv.size
+    if K < 2:
+        _refuse(site, "a mixture of fewer than 2 components")
+    if tuple(comp.batch_shape) not in ((), (K,)):
+        _refuse(site, f"component batch shape {tuple(comp.batch_shape)} under {K} mixing weights")
+    logw = B.ew("log", w) if isinstance(mixing, dist.CategoricalProbs) else w - B.logsumexp(w, 1, K)
+    col = np.tile(np.arange(K), N)  # the component of each element of the flat table
+    d = {}
+    for p in entry[1]:
+        val = lower(getattr(comp, p), site)
+        if val.n not in (1, K):
+            _refuse(site, f"component parameter {p!r} of {val.n} elements under {K} mixing weights")
+        d[p] = B.gather(val, col) if val.n == K else val  # a scalar keeps stride 0
+    x = B.const(np.repeat(xv, K))
+    with np.errstate(all="ignore"):
+        logx = B.const(np.log(x.c)) if comp.support == "positive" else None
+    table = B.gather(logw, col)
+    for t in entry[0](B, d, x, logx):
+        table = table + t
+    return [B.rsum(B.logsumexp(table, N, K))]
+
+
 # distribution -> (expansion, parameter names, may be latent)
 _LOGPROB = {
     dist.Normal: (_lp_normal, ("loc", "scale"), True),
@@ -552,10 +703,17 @@ _LOGPROB = {
     dist.Pareto: (_lp_pareto, ("scale", "alpha"), True),
     dist.BinomialProbs: (_lp_binomial_probs, ("total_count", "probs"), False),
     dist.BinomialLogits: (_lp_binomial_logits, ("total_count", "logits"), False),
+    dist.Dirichlet: (_lp_dirichlet, ("concentration",), True),
+    dist.CategoricalProbs: (_lp_categorical_probs, ("probs",), False),
+    dist.CategoricalLogits: (_lp_categorical_logits, ("logits",), False),
+    dist.MixtureSameFamily: (None, (), False),  # _lp_mixture lowers the two distributions it holds
 }
 _BINOMIAL = (dist.BinomialProbs, dist.BinomialLogits)
+# whole-vector distributions: one log density per site, returned as scalar terms
+_VECTOR = (dist.Dirichlet, dist.CategoricalProbs, dist.CategoricalLogits, dist.MixtureSameFamily)
 # support -> transform code of a latent site
-_SUPPORT_CODE = {"real": REAL, "positive": POSITIVE, "unit_interval": UNIT, "interval": UNIT, "greater_than": LOWER}
+_SUPPORT_CODE = {"real": REAL, "positive": POSITIVE, "unit_interval": UNIT, "interval": UNIT, "greater_than": LOWER,
+                 "simplex": SIMPLEX}
 
 
 def _site_bounds(base, name):
@@ -624,6 +782,20 @@ class _Lowering:
             return B.ew(op, self(x.args[0], site), self(x.args[1], site))
         if op == "sum":
             return B.rsum(self(x.args[0], site))
+        if op == "cumsum":
+            return B.cumsum(self(x.args[0], site))
+        if op == "logsumexp":
+            v = self(x.args[0], site)
+            return B.logsumexp(v, 1, v.n)
+        if op == "concatenate":
+            parts = [self(a, site) for a in x.args]
+            for a, v in zip(x.args, parts):
+                if v.n != int(np.prod(np.shape(_host(a)) if not isinstance(a, Sym) else a.shape, dtype=np.int64)):
+                    _refuse(site, "concatenate of a part whose size is not its shape's")
+            out = parts[0]
+            for v in parts[1:]:
+                out = B.concat(out, v)
+            return out
         if op == "getitem":
             src, idx = self(x.args[0], site), x.args[1]
             sel = np.arange(src.n)[idx] if isinstance(idx, (int, slice)) else np.asarray(_host(idx))
@@ -646,7 +818,7 @@ class _Lowering:
                               f"{np.shape(_host(b)) if not isinstance(b, Sym) else b.shape}")
             return B.matvec(M, vec)
         _refuse(site, f"operation {op!r} is not supported (supported: {sorted(_UNARY[:7] + _BINARY)}, expit, sum, "
-                      "getitem, matmul)")
+                      "cumsum, logsumexp, concatenate, getitem, matmul)")
 
 
 def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
@@ -672,12 +844,18 @@ def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
         n = int(np.prod(s.shape, dtype=np.int64))
         if n <= 0:
             _refuse(s.name, "empty site")
+        shape = tuple(s.shape)
+        if base.support == "simplex":  # K - 1 unconstrained coordinates: the site's shape in `sites`
+            if len(shape) != 1 or shape != tuple(base.event_shape) or n < 2:
+                _refuse(s.name, f"a simplex site of shape {shape} (supported: one vector of K >= 2 components, "
+                                "without batch or plate dimensions)")
+            n, shape = n - 1, (n - 1,)
         bounds = _site_bounds(base, s.name)
         if bounds is not None:
             if any(b.size not in (1, n) for b in bounds):
                 _refuse(s.name, f"bounds of {[b.size for b in bounds]} elements at a site of {n}")
             affine[s.name] = bounds
-        sites.append((s.name, tuple(s.shape), _SUPPORT_CODE[base.support]))
+        sites.append((s.name, shape, _SUPPORT_CODE[base.support]))
         offsets[s.name] = (o, n)
         o += n
     B = _Builder(o)
@@ -699,6 +877,17 @@ def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
             constrained[name] = B.ew("add", lo, B.ew("mul", width, x))
             log_value[name] = logx if constrained[name] is x else None
             log_jac[name] = [logx, log1mx, B.const(np.log(width))]
+        elif tr == SIMPLEX:
+            # stick breaking with the reference's offset (StickBreakingTransform: u = 0 is the uniform
+            # point), in log space: t = u - log(K - 1 - k), log z = -softplus(-t), log(1 - z) =
+            # -softplus(t), log x = (log z, 0) + (0, cumsum log(1 - z)).  log|J| = sum_{k < K-1}
+            # (log x_k + log(1 - z_k)), and the second terms sum to the scan's last element log x_{K-1}:
+            # log|J| = sum(log x) over all K.  x = exp(log x), so every log x of a density folds back
+            # to log x itself (ew: log(exp(v)) = v) and never sees an underflowed x.
+            t = u - np.log(np.arange(u.n, 0, -1, dtype=np.float64))
+            log_z, log_1mz = -B.ew("softplus", -t), -B.ew("softplus", t)
+            logx = B.concat(log_z, B.const([0.0])) + B.concat(B.const([0.0]), B.cumsum(log_1mz))
+            constrained[name], log_value[name], log_jac[name] = B.ew("exp", logx), logx, [B.rsum(logx)]
         else:  # LOWER: x = lo + exp(u), log|J| = u
             constrained[name], log_value[name], log_jac[name] = B.ew("add", lo, B.ew("exp", u)), None, [u]
     lower = _Lowering(B, constrained)
@@ -725,9 +914,14 @@ def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
                     _refuse(s.name, f"observations of shape {xv.shape}: rank > 1 is not supported")
                 x = B.const(xv)
                 with np.errstate(all="ignore"):
-                    logx = B.const(np.log(x.c)) if base.support == "positive" else None
+                    logx = B.const(np.log(x.c)) if base.support in ("positive", "simplex") else None
                 n_site = max(int(np.prod(s.shape, dtype=np.int64)), x.n)
-            terms = expand(B, d, x, logx)
+            if isinstance(base, _VECTOR):
+                n_site = 1
+            if isinstance(base, dist.MixtureSameFamily):
+                terms = _lp_mixture(B, lower, base, np.asarray(x.c, np.float64).reshape(-1), s.name)
+            else:
+                terms = expand(B, d, x, logx)
             if s.obs is None:
                 terms += log_jac[s.name]
         except _Refuse:
