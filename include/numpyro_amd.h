@@ -630,6 +630,57 @@ size_t nmx_predict_program_workspace_bytes(int num_slots, int num_samples);
 int nmx_predict_program(const nmx_program* program, const float* samples, int num_samples,
                         int64_t sample_offset, uint64_t seed, float* tape, void* stream);
 
+/* ---- log-likelihood programs: log_likelihood for any traced model of the program compiler's
+ *      class (numpyro_amd/loglik_program.py compile_log_likelihood).  The predictive program
+ *      format without draw ops: slots [0, dim) hold the sample's given sites, and each output
+ *      { slot, n, column } is the elementwise log density of one observed site, copied by the
+ *      kernel from the sample's tape row into columns [column, column + n) of row s of a dense
+ *      table out[num_samples][ldo].
+ *
+ * The pointwise reductions take such a table (any f32 table [rows][ld]) and give per column
+ *   lppd   = logsumexp over rows - log S     (S the number of rows accumulated)
+ *   p_waic = sum (x - mean)^2 / (S - 1)      (the unbiased variance over rows)
+ * through a running per-column state, so the rows may arrive in chunks, one accumulate call after
+ * another.  The state of a column is { m, s, n, mean, M2 }: m the largest entry so far, s = sum
+ * exp(x - shift(m)) with shift(m) = m, or 0 where m is not finite, and Welford's mean and M2.
+ * Two states merge (a holds the earlier rows) as m = max, s = s_a exp(shift(m_a) - shift(m)) +
+ * s_b exp(shift(m_b) - shift(m)) (a state with m = -inf contributes s * 0), and by Chan:
+ * delta = mean_b - mean_a, mean = mean_a + delta (n_b / n), M2 = (M2_a + M2_b) + delta^2 (n_a n_b / n).
+ * A chunk of R rows is cut into splits of max(NMX_POINTWISE_MIN_SPLIT_ROWS, ceil(R /
+ * NMX_POINTWISE_MAX_SPLITS)) consecutive rows.  With 64 columns or more a lane owns a column and
+ * pushes the split's rows in order.  With fewer, cpad = the power of two >= num_columns and
+ * G = 64 / cpad: row group g pushes the rows g, g + G, ... of the split, and the G states merge by
+ * halving (state g with state g + G/2, the lower first, then G/4, ...).  The splits' states of a
+ * column, padded with empty states to NMX_POINTWISE_MAX_SPLITS, merge by the same halving (split q
+ * with split q + 32, then 16, ...; an empty state leaves the other as it is), and the running
+ * state is merged with the result.  Every order is fixed by the shapes: no atomics, and two runs
+ * are bitwise equal.  Special columns:
+ *   p_waic is NaN for S = 1, and NaN in a column that holds a non-finite entry;
+ *   lppd is -inf for a column of all -inf, finite if the column has a finite entry and no +inf or
+ *   NaN, and NaN if the column holds a NaN.
+ * ---- */
+#define NMX_POINTWISE_MAX_SPLITS 64
+#define NMX_POINTWISE_MIN_SPLIT_ROWS 16
+/* Validate a log-likelihood program in HOST memory, as nmx_predict_program_check does, and refuse
+ * any draw op; `outputs` is num_outputs x { slot, n, column }: each { slot, n } as a predictive
+ * output, its columns inside [0, ldo), no two outputs sharing a column.  Needs no GPU. */
+int nmx_loglik_program_check(const nmx_program* host_program, const int32_t* outputs, int num_outputs, int64_t ldo);
+/* One launch, one wave per sample: row s of `out` [num_samples][ldo] receives the outputs of the
+ * program run on row s of `samples` [num_samples][dim] (NULL when dim = 0).  `tape` is
+ * nmx_predict_program_workspace_bytes(num_slots, num_samples); `program` and `outputs` hold DEVICE
+ * arrays of a program and an output list the check accepted with this ldo. */
+int nmx_loglik_program(const nmx_program* program, const float* samples, int num_samples, const int32_t* outputs,
+                       int num_outputs, float* tape, float* out, int64_t ldo, void* stream);
+/* The state of the pointwise reductions over num_columns columns (the running state and the
+ * splits' partial states). */
+size_t nmx_pointwise_state_bytes(int num_columns);
+/* Accumulate the rows of table [num_rows][ld] (ld >= num_columns) into `state`; first != 0 starts
+ * the state anew.  Two launches. */
+int nmx_pointwise_accumulate(const float* table, int num_rows, int64_t ld, int num_columns, void* state, int first,
+                             void* stream);
+/* lppd [num_columns] and p_waic [num_columns] (either may be NULL) of the rows accumulated. */
+int nmx_pointwise_finish(const void* state, int num_columns, float* lppd, float* p_waic, void* stream);
+
 /* ---- self tests (no reference counterpart; used by tests and smoke()) ---- */
 /* Philox4x32-10 on device: ctr_key is n x {c0,c1,c2,c3,k0,k1}, out is n x 4 words. */
 int nmx_selftest_philox(const uint32_t* ctr_key, uint32_t* out, int n, void* stream);

@@ -10,7 +10,7 @@ from itertools import product
 import numpy as np
 
 __all__ = ["autocorrelation", "autocovariance", "effective_sample_size", "gelman_rubin", "hpdi",
-           "split_gelman_rubin", "summary", "print_summary", "print_summary_table"]
+           "split_gelman_rubin", "summary", "print_summary", "print_summary_table", "lppd", "waic"]
 
 
 def _np(x):
@@ -158,3 +158,45 @@ def print_summary_table(table, prob=0.90):
                 label = name + "[{}]".format(",".join(map(str, idx)))
                 print(row_fmt.format(label, *[float(v[idx]) for v in stats.values()]))
     print()
+
+
+# ----------------------------------------------------------------------------- predictive accuracy
+def _pointwise(log_lik):
+    """(lppd_i, p_waic_i) float32 device tensors of a table [S, ...] or a dict of such tables."""
+    from .pointwise import reduce_table
+
+    if isinstance(log_lik, dict):
+        if not log_lik:
+            raise ValueError("an empty dict of log-likelihood tables")
+        parts = {k: reduce_table(v) for k, v in log_lik.items()}
+        return {k: v[0] for k, v in parts.items()}, {k: v[1] for k, v in parts.items()}
+    return reduce_table(log_lik)
+
+
+def lppd(log_lik):
+    """Log pointwise predictive density per observation of a log-likelihood table [S, ...] (the
+    result of infer.log_likelihood; a dict of tables gives a dict): logsumexp over the S samples
+    minus log S, reduced by the pointwise HIP kernels (numpyro_amd/pointwise.py).  A float32 tensor
+    of the table's trailing shape on the current GPU."""
+    return _pointwise(log_lik)[0]
+
+
+def waic(log_lik):
+    """Widely applicable information criterion of a log-likelihood table [S, ...] or a dict of
+    tables (their observations pooled), on the log score scale (Watanabe 2010; Vehtari, Gelman and
+    Gabry 2017, eqs. 11-13): elpd_i = lppd_i - p_waic_i with p_waic_i the variance over samples
+    (S - 1) of the log likelihood of observation i.  Returns {"elpd_waic": sum elpd_i, "p_waic":
+    sum p_waic_i, "lppd": sum lppd_i, "se": sqrt(n var(elpd_i))} (the population variance over the n
+    observations) as float64 tensors; the per-observation figures come from the pointwise HIP
+    kernels, the sums over observations are torch."""
+    import torch
+
+    lp, pw = _pointwise(log_lik)
+    if isinstance(lp, dict):
+        lp = torch.cat([v.reshape(-1) for v in lp.values()])
+        pw = torch.cat([v.reshape(-1) for v in pw.values()])
+    lp, pw = lp.reshape(-1).double(), pw.reshape(-1).double()
+    elpd = lp - pw
+    n = elpd.numel()
+    return {"elpd_waic": elpd.sum(), "p_waic": pw.sum(), "lppd": lp.sum(),
+            "se": torch.sqrt(n * elpd.var(unbiased=False))}

@@ -1,0 +1,157 @@
+"""``log_likelihood`` and ``pointwise_predictive``: the log density of every observed site at
+each posterior sample, for model functions of the program compiler's class.
+
+Mirrors ``numpyro.infer.log_likelihood`` (numpyro/infer/util.py:1094-1170): called with the model,
+a dict of posterior samples (``MCMC.get_samples()``, leading batch dims per ``batch_ndims``) and
+the model's arguments, data included, it returns ``{observed site: [*batch_shape, *site_shape]}``.
+The reference re-runs the model once per sample under ``substitute``; here the model is traced
+once and lowered to a draw-free program (numpyro_amd/loglik_program.py compile_log_likelihood)
+that one HIP kernel runs once per sample, writing a dense table (csrc/loglik_program.hip).
+
+Nearly every use reduces that table over the samples (the log pointwise predictive density that
+examples/baseball.py prints, WAIC): ``pointwise_predictive`` streams the same chunks through the
+pointwise reduce kernels and returns the per-observation lppd and p_waic without holding the
+table.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from .. import native
+from .. import potentials as P
+from ..native import check, lib, ptr
+from ..pointwise import PointwiseReducer
+
+# the tape of one chunk of samples stays under this many bytes
+MAX_WORKSPACE_BYTES = 1 << 30
+
+
+def _flatten(model, posterior_samples, batch_ndims, what):
+    if isinstance(model, P.FusedModel):
+        raise NotImplementedError(f"{what}: {model!r} is a FusedModel object, not a model function; pass the model "
+                                  "written with numpyro_amd.sample (it is traced the program way)")
+    if not callable(model):
+        raise NotImplementedError(f"{what}: {model!r} is not a model function")
+    if batch_ndims not in (0, 1, 2):
+        raise ValueError(f"batch_ndims must be 0, 1 or 2, got {batch_ndims}")
+    batch_shape = proto = None
+    for name, v in posterior_samples.items():
+        shp = tuple(np.shape(v)[:batch_ndims])
+        if len(shp) < batch_ndims:
+            raise ValueError(f"site {name} has shape {tuple(np.shape(v))}, fewer than batch_ndims = {batch_ndims} dimensions")
+        if batch_shape is not None and shp != batch_shape:
+            raise ValueError(f"Batch shapes at site {name} and {proto} should be the same, "
+                             f"but got {shp} and {batch_shape}")
+        if batch_shape is None:
+            batch_shape, proto = shp, name
+    if batch_shape is None:
+        raise ValueError("No sample sites in posterior samples to infer `num_samples`.")
+    S = int(math.prod(batch_shape))
+    if S <= 0:
+        raise ValueError(f"posterior samples of batch shape {batch_shape} hold no sample")
+    flat = {k: torch.as_tensor(v if torch.is_tensor(v) else np.asarray(v)) for k, v in posterior_samples.items()}
+    flat = {k: v.reshape(S, *v.shape[batch_ndims:]) for k, v in flat.items()}
+    return flat, batch_shape, S
+
+
+class _Run:
+    """A compiled log-likelihood program bound to a device: its arrays uploaded, the samples
+    flattened to [S, dim], and the chunking under MAX_WORKSPACE_BYTES."""
+
+    def __init__(self, model, posterior_samples, args, kwargs, batch_ndims, what):
+        from ..loglik_program import compile_log_likelihood
+
+        flat, self.batch_shape, self.S = _flatten(model, posterior_samples, batch_ndims, what)
+        self.prog = prog = compile_log_likelihood(model, args, kwargs, given=flat)
+        for name, _, n, shape in prog.inputs:
+            if tuple(flat[name].shape[1:]) != tuple(shape):
+                raise ValueError(f"posterior samples of site {name!r} have shape {tuple(flat[name].shape[1:])} per "
+                                 f"draw, the model's site has {tuple(shape)}")
+        if torch.cuda.is_available():
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        elif prog.num_ops:
+            raise RuntimeError(f"{what} needs a GPU (the program runs on a HIP kernel)")
+        else:
+            self.device = torch.device("cpu")  # every log density is a host constant
+        if not prog.num_ops:
+            return
+        st, msg = prog.native_check()  # a malformed program never reaches the device
+        if st:
+            raise native.NativeError(f"nmx_loglik_program_check failed (status {st}): {msg}")
+        S, dev = self.S, self.device
+        self.x = (torch.cat([flat[name].to(dev, torch.float32).reshape(S, n) for name, _, n, _ in prog.inputs], 1)
+                  .contiguous() if prog.inputs else None)
+        row_bytes = lib().nmx_predict_program_workspace_bytes(prog.num_slots, 1)
+        self.chunk = min(S, MAX_WORKSPACE_BYTES // row_bytes)
+        if self.chunk <= 0:
+            raise NotImplementedError(f"{what}: one sample's tape of {prog.num_slots} slots needs {row_bytes} bytes, "
+                                      f"above MAX_WORKSPACE_BYTES = {MAX_WORKSPACE_BYTES}")
+        self.d_ops = torch.from_numpy(prog.ops).to(dev)
+        self.d_consts = torch.from_numpy(prog.consts).to(dev)
+        self.d_index = torch.from_numpy(prog.index).to(dev) if prog.index.size else None
+        self.d_outputs = torch.from_numpy(prog.output_table()).to(dev)
+        self.cprog = native.Program(ops=ptr(self.d_ops), consts=ptr(self.d_consts), index=ptr(self.d_index),
+                                    num_ops=prog.num_ops, num_slots=prog.num_slots, num_consts=prog.consts.size,
+                                    num_index=prog.index.size, dim=prog.dim)
+        self.tape = torch.empty(self.chunk, prog.num_slots, dtype=torch.float32, device=dev)
+
+    def chunks(self):
+        return [(s0, min(self.chunk, self.S - s0)) for s0 in range(0, self.S, self.chunk)]
+
+    def launch(self, s0, m, out):
+        """Samples [s0, s0 + m) into the rows of ``out`` [>= m, num_columns]."""
+        prog = self.prog
+        check(lib().nmx_loglik_program(ctypes.byref(self.cprog), ptr(self.x[s0:]) if self.x is not None else None, m,
+                                       ptr(self.d_outputs), len(prog.outputs), ptr(self.tape), ptr(out),
+                                       prog.num_columns, native.stream_ptr()), "nmx_loglik_program")
+
+    def constant(self, c):
+        return torch.as_tensor(np.asarray(c, np.float32)).to(self.device)
+
+
+def log_likelihood(model, posterior_samples, *args, parallel=False, batch_ndims=1, **kwargs):
+    """numpyro.infer.log_likelihood (numpyro/infer/util.py:1094-1170) for model functions of the
+    program compiler's class: {observed site: float32 tensor [*batch_shape, *site_shape]} on the
+    current GPU.  ``parallel`` is accepted and ignored (every sample is one wave of one launch)."""
+    run = _Run(model, posterior_samples, args, kwargs, batch_ndims, "log_likelihood")
+    prog, S = run.prog, run.S
+    out = {}
+    if prog.num_ops:
+        table = torch.empty(S, prog.num_columns, dtype=torch.float32, device=run.device)
+        for s0, m in run.chunks():
+            run.launch(s0, m, table[s0:])
+        for o in prog.outputs:
+            v = table[:, o.column:o.column + o.n]
+            out[o.name] = v.reshape(S, *((o.n,) if o.shape else ())).expand(S, *o.shape).contiguous()
+    for name, c in prog.constant_outputs.items():
+        out[name] = run.constant(c).expand(S, *np.shape(c)).contiguous()
+    return {name: v.reshape((*run.batch_shape, *v.shape[1:])) for name, v in out.items()}
+
+
+def pointwise_predictive(model, posterior_samples, *args, batch_ndims=1, **kwargs):
+    """{observed site: {"lppd": [*site_shape], "p_waic": [*site_shape]}}: per observation, the log
+    pointwise predictive density logsumexp_s(log p(y_i | theta_s)) - log S and the variance over s
+    of log p(y_i | theta_s) (S - 1 in the denominator: NaN for one sample), reduced on the device
+    chunk by chunk without holding the [S, N] table."""
+    run = _Run(model, posterior_samples, args, kwargs, batch_ndims, "pointwise_predictive")
+    prog, S = run.prog, run.S
+    out = {}
+    if prog.num_ops:
+        red = PointwiseReducer(prog.num_columns, run.device)
+        table = torch.empty(run.chunk, prog.num_columns, dtype=torch.float32, device=run.device)
+        for s0, m in run.chunks():  # stream order: the reduce reads the chunk before the next launch writes it
+            run.launch(s0, m, table)
+            red.accumulate(table[:m])
+        lppd, p_waic = red.finish()
+        for o in prog.outputs:
+            out[o.name] = {k: v[o.column:o.column + o.n].reshape((o.n,) if o.shape else ()).expand(o.shape).contiguous()
+                           for k, v in (("lppd", lppd), ("p_waic", p_waic))}
+    for name, c in prog.constant_outputs.items():
+        # S equal values: their logsumexp - log S is the value, their variance 0
+        c = run.constant(c)
+        out[name] = {"lppd": c, "p_waic": torch.full_like(c, 0.0 if S > 1 else float("nan"))}
+    return out

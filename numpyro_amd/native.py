@@ -125,6 +125,8 @@ BINOMIAL_MAX_STEPS = 96  # NMX_BINOMIAL_MAX_STEPS
 BINOMIAL_BTRS_MEAN = 10.0  # NMX_BINOMIAL_BTRS_MEAN
 BINOMIAL_MAX_COUNT = 1 << 24  # NMX_BINOMIAL_MAX_COUNT
 DRAW_MAX_ELEMENTS = 1 << 24  # the counter's element field
+POINTWISE_MAX_SPLITS = 64  # NMX_POINTWISE_MAX_SPLITS
+POINTWISE_MIN_SPLIT_ROWS = 16  # NMX_POINTWISE_MIN_SPLIT_ROWS
 
 
 class Program(ctypes.Structure):
@@ -185,6 +187,11 @@ SIGNATURES: dict[str, tuple] = {
     "nmx_predict_program_check": (c_int, [_progp, c_vp, c_int]),
     "nmx_predict_program_workspace_bytes": (c_size, [c_int, c_int]),
     "nmx_predict_program": (c_int, [_progp, c_vp, c_int, c_i64, c_u64, c_vp, c_vp]),
+    "nmx_loglik_program_check": (c_int, [_progp, c_vp, c_int, c_i64]),
+    "nmx_loglik_program": (c_int, [_progp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_i64, c_vp]),
+    "nmx_pointwise_state_bytes": (c_size, [c_int]),
+    "nmx_pointwise_accumulate": (c_int, [c_vp, c_int, c_i64, c_int, c_vp, c_int, c_vp]),
+    "nmx_pointwise_finish": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp]),
     "nmx_logreg_packed_bytes": (c_size, [c_i64, c_int]),
     "nmx_logreg_pack": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     "nmx_logreg_workspace_bytes": (c_size, [c_i64, c_int, c_int]),

@@ -638,9 +638,18 @@ def _category_index(x, K):
     return idx.astype(np.int64)
 
 
-def _lp_categorical_probs(B, d, x, logx):
+def _ew_categorical_probs(B, d, x, logx):
     p = d["probs"]
-    return [B.rsum(B.gather(B.ew("log", p), _category_index(x, p.n)))]
+    return [B.gather(B.ew("log", p), _category_index(x, p.n))]
+
+
+def _lp_categorical_probs(B, d, x, logx):
+    return [B.rsum(t) for t in _ew_categorical_probs(B, d, x, logx)]
+
+
+def _ew_categorical_logits(B, d, x, logx):
+    lg = d["logits"]
+    return [B.gather(lg, _category_index(x, lg.n)), -B.logsumexp(lg, 1, lg.n)]
 
 
 def _lp_categorical_logits(B, d, x, logx):
@@ -653,8 +662,13 @@ _CATEGORICAL = (dist.CategoricalProbs, dist.CategoricalLogits)
 
 
 def _lp_mixture(B, lower, base, xv, site):
+    """MixtureSameFamily at observations xv [N]: the site's total, the sum of _ew_mixture."""
+    return [B.rsum(t) for t in _ew_mixture(B, lower, base, xv, site)]
+
+
+def _ew_mixture(B, lower, base, xv, site):
     """MixtureSameFamily at observations xv [N]: the N x K table of component log densities plus
-    log weights, flat and row-major, through logsumexp(rows = N, cols = K), then summed."""
+    log weights, flat and row-major, through logsumexp(rows = N, cols = K): N elements."""
     mixing, comp = _base(base.mixing_distribution), _base(base.component_distribution)
     if not isinstance(mixing, _CATEGORICAL):
         _refuse(site, f"a mixing distribution {type(mixing).__name__} (a Categorical is supported)")
@@ -682,7 +696,7 @@ def _lp_mixture(B, lower, base, xv, site):
     table = B.gather(logw, col)
     for t in entry[0](B, d, x, logx):
         table = table + t
-    return [B.rsum(B.logsumexp(table, N, K))]
+    return [B.logsumexp(table, N, K)]
 
 
 # distribution -> (expansion, parameter names, may be latent)
@@ -711,6 +725,28 @@ _LOGPROB = {
 _BINOMIAL = (dist.BinomialProbs, dist.BinomialLogits)
 # whole-vector distributions: one log density per site, returned as scalar terms
 _VECTOR = (dist.Dirichlet, dist.CategoricalProbs, dist.CategoricalLogits, dist.MixtureSameFamily)
+
+
+# ---- the logit likelihoods elementwise.  x eta - n softplus(eta) is right as a term of a site's
+# total, but one element alone cancels where the outcome is all but certain (x = n, eta large:
+# eta - softplus(eta) = -softplus(-eta), 1e-9 from operands of 20).  The same density without a
+# difference: -x softplus(-eta) - (n - x) softplus(eta).
+def _ew_bernoulli_logits(B, d, x, logx, n=1.0):
+    eta = d["logits"]
+    return [-(x * B.ew("softplus", -eta)), -((n - x) * B.ew("softplus", eta))]
+
+
+def _ew_binomial_logits(B, d, x, logx):
+    n = d["total_count"]
+    return _ew_bernoulli_logits(B, d, x, logx, n) + [_binomial_coefficient(B, n, x)]
+
+
+# elementwise expansions where they differ from _LOGPROB's (loglik_program.py): the whole-vector
+# distributions before their final rsum, one term list of N elements per site (a Dirichlet vector
+# is one observation: its _lp terms are its elementwise ones), and the logit likelihoods
+_ELEMENTWISE = {dist.CategoricalProbs: _ew_categorical_probs, dist.CategoricalLogits: _ew_categorical_logits,
+                dist.Dirichlet: _lp_dirichlet, dist.BernoulliLogits: _ew_bernoulli_logits,
+                dist.BinomialLogits: _ew_binomial_logits}
 # support -> transform code of a latent site
 _SUPPORT_CODE = {"real": REAL, "positive": POSITIVE, "unit_interval": UNIT, "interval": UNIT, "greater_than": LOWER,
                  "simplex": SIMPLEX}
