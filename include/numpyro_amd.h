@@ -568,7 +568,8 @@ int nmx_predict_bnn(const float* X, int n, int dx, int dh, int dy, const float* 
  *     normal of (w(t).x, w(t).y), v = (1 + c x)^3, accepted when 1 + c x > 0 and
  *     log u01_open0(w(t).z) < x^2 / 2 + d - d v + d log v; the value is d v, times
  *     exp(log(u01_open0(w(t).w)) / a) when a < 1.
- *   NMX_DRAW_POISSON (a = rate; NaN unless 0 <= rate < inf; 0 at rate 0):
+ *   NMX_DRAW_POISSON (a = rate; NaN unless 0 <= rate < NMX_POISSON_MAX_RATE = 2^24, where f32
+ *     stops holding every whole number; 0 at rate 0):
  *     rate < 10: inversion of u = u01(w(0).x): the first k with u <= sum_{j <= k} p_j, p_0 =
  *       exp(-rate), p_j = p_{j-1} rate / j, or the first k > rate with p_k < 2^-40 (the tail
  *       left is below the 2^-24 resolution of u), k < NMX_POISSON_MAX_STEPS;
@@ -576,7 +577,11 @@ int nmx_predict_bnn(const float* X, int n, int dx, int dh, int dy, const float* 
  *       b = 0.931 + 2.53 sqrt(rate), a = -0.059 + 0.02483 b, 1/alpha = 1.1239 + 1.1328 / (b - 3.4),
  *       v_r = 0.9277 - 3.6224 / (b - 2), us = 0.5 - |U|, k = floor((2 a / us + b) U + rate + 0.43);
  *       accepted when us >= 0.07 and V <= v_r; rejected when k < 0 or (us < 0.013 and V > us);
- *       else accepted when log(V / alpha / (a / us^2 + b)) <= -rate + k log rate - lgamma(k + 1).
+ *       else accepted when log(V / alpha / (a / us^2 + b)) <= log pmf(k), taken with k1 = k + 1 as
+ *         k log1p((rate - k1) / k1) - (rate - k1) - log(k1) / 2 - log(2 pi) / 2 - tail(k)
+ *       (tail below).  This is -rate + k log rate - lgamma(k + 1) with log k! as the Stirling
+ *       formula at k1 plus its tail: in that form the terms of size k log k cancel in f32 and
+ *       leave noise from rate 1e5 on (one ulp of 1.4e7 is 1).
  *   NMX_DRAW_UNIFORM:     u01(w(0).x)
  *   NMX_DRAW_BINOMIAL (a = total count n, b = probability p; the structure of
  *     numpyro/distributions/util.py:20-181).  Before any loop: NaN when n or p is NaN, p is
@@ -593,15 +598,18 @@ int nmx_predict_bnn(const float* X, int n, int dx, int dh, int dy, const float* 
  *     n q >= 10: Hoermann's BTRS (1993), attempt t with U = u01(w(t).x) - 0.5, V =
  *       u01_open0(w(t).y): spq = sqrt(n q (1 - q)), c = n q + 0.5, b = 1.15 + 2.53 spq,
  *       a = -0.0873 + 0.0248 b + 0.01 q, alpha = (2.83 + 5.1 / b) spq, v_r = 0.92 - 4.2 / b,
- *       m = floor((n + 1) q), lq = log(q) - log1p(-q), us = 0.5 - |U|,
- *       k = floor((2 a / us + b) U + c);
+ *       m = floor((n + 1) q), us = 0.5 - |U|, k = floor((2 a / us + b) U + c);
  *       accepted when us >= 0.07 and V <= v_r; rejected unless 0 <= k <= n; else accepted when
  *       log(V alpha / (a / us^2 + b)) <= (n + 1) log1p((k - m) / (n - k + 1))
- *         + (k + 0.5) (log((n - k + 1) / (k + 1)) + lq) + (tail(k) - tail(n - k))
- *         + (m + 0.5) (log((m + 1) / (n - m + 1)) - lq) + (tail(m) + tail(n - m)),
+ *         + (k + 0.5) lo(k) + (tail(k) - tail(n - k)) - (m + 0.5) lo(m) + (tail(m) + tail(n - m)),
+ *       lo(j) = log((n - j + 1) q / ((j + 1) (1 - q)))
+ *             = log1p((fma(n, q, -j) + (2 q - 1)) / ((j + 1) (1 - q))),
  *       tail(j) = log(j!) - the Stirling formula at j + 1: a table of ten values for j < 10, else
  *       (1/12 - (1/360 - 1/1260 / (j+1)^2) / (j+1)^2) / (j+1).  (log((n-m+1) / (n-k+1)) is taken
- *       as log1p of an exact integer ratio: in f32 the direct form loses n ulp.)
+ *       as log1p of an exact integer ratio: in f32 the direct form loses n ulp.  lo(j) is one
+ *       log1p for the same reason: as log((n - j + 1) / (j + 1)) + log(q / (1 - q)) the two logs
+ *       cancel near the mode and the quotient's rounding, times j, reaches 1 at counts near
+ *       2^24; n q - j is one fused multiply-add, rounded once.)
  * ---- */
 enum nmx_draw_opcode {
   NMX_DRAW_NORMAL = 64, NMX_DRAW_EXPONENTIAL, NMX_DRAW_CAUCHY,  /* no parameter */
@@ -613,6 +621,7 @@ enum nmx_draw_opcode {
 #define NMX_DRAW_MAX_ATTEMPTS 64
 #define NMX_POISSON_MAX_STEPS 96
 #define NMX_POISSON_PTRS_RATE 10.0f
+#define NMX_POISSON_MAX_RATE 16777216.0f /* 2^24 */
 #define NMX_BINOMIAL_MAX_STEPS 96
 #define NMX_BINOMIAL_BTRS_MEAN 10.0f
 #define NMX_BINOMIAL_MAX_COUNT 16777216.0f /* 2^24 */

@@ -341,9 +341,24 @@ __device__ __forceinline__ float nmx_draw_gamma(float a, uint64_t seed, uint32_t
   return NAN;
 }
 
+// log(j!) minus the Stirling formula at j + 1 (Hoermann 1993, the f(k) of BTRS), j >= 0 whole
+static __device__ const float NMX_STIRLING_TAIL[10] = {
+    0.08106146679532726f, 0.04134069595540929f, 0.02767792568499834f, 0.02079067210376509f, 0.01664469118982119f,
+    0.01387612882307075f, 0.01189670994589177f, 0.01041126526197209f, 0.009255462182712733f, 0.008330563433362871f};
+
+__device__ __forceinline__ float nmx_stirling_tail(float j) {
+  if (j < 10.0f) return NMX_STIRLING_TAIL[(int)j];
+  const float r = 1.0f / (j + 1.0f), r2 = r * r;
+  return (1.0f / 12 - (1.0f / 360 - (1.0f / 1260) * r2) * r2) * r;
+}
+
+// The slow acceptance compares with log pmf(k) = -rate + k log rate - log k!, whose terms are of
+// size k log k (1.4e7 at rate 1e6, where one f32 ulp is 1) and whose value is of order 1.  With
+// log k! as the Stirling formula at k1 = k + 1 plus its tail they cancel inside one log1p:
+//   k log1p((rate - k1) / k1) - (rate - k1) - log(k1) / 2 - log(2 pi) / 2 - tail(k)
 __device__ __forceinline__ float nmx_draw_poisson(float rate, uint64_t seed, uint32_t s, uint32_t stream,
                                                   uint32_t i) {
-  if (!(rate >= 0.0f) || rate == INFINITY) return NAN;
+  if (!(rate >= 0.0f && rate < NMX_POISSON_MAX_RATE)) return NAN;
   if (rate == 0.0f) return 0.0f;
   if (rate < NMX_POISSON_PTRS_RATE) {
     const float u = nmx_u01(nmx_rng(seed, s, stream, NMX_EV_PREDICT, i, 0).x);
@@ -357,7 +372,7 @@ __device__ __forceinline__ float nmx_draw_poisson(float rate, uint64_t seed, uin
     }
     return NAN;
   }
-  const float log_rate = logf(rate), b = 0.931f + 2.53f * sqrtf(rate), a = -0.059f + 0.02483f * b;
+  const float b = 0.931f + 2.53f * sqrtf(rate), a = -0.059f + 0.02483f * b;
   const float inv_alpha = 1.1239f + 1.1328f / (b - 3.4f), v_r = 0.9277f - 3.6224f / (b - 2.0f);
   for (uint32_t t = 0; t < NMX_DRAW_MAX_ATTEMPTS; ++t) {
     const nmx_u4 w = nmx_rng(seed, s, stream, NMX_EV_PREDICT, i, t);
@@ -366,25 +381,23 @@ __device__ __forceinline__ float nmx_draw_poisson(float rate, uint64_t seed, uin
     const float k = floorf((2.0f * a / us + b) * U + rate + 0.43f);
     if (us >= 0.07f && V <= v_r) return k;
     if (!(k >= 0.0f) || (us < 0.013f && V > us)) continue;
-    if (logf(V * inv_alpha / (a / (us * us) + b)) <= -rate + k * log_rate - lgammaf(k + 1.0f)) return k;
+    const float k1 = k + 1.0f, excess = rate - k1;
+    const float log_pmf =
+        k * log1pf(excess / k1) - excess - 0.5f * logf(k1) - 0.9189385332046727f - nmx_stirling_tail(k);
+    if (logf(V * inv_alpha / (a / (us * us) + b)) <= log_pmf) return k;
   }
   return NAN;
 }
 
-// log(j!) minus the Stirling formula at j + 1 (Hoermann 1993, the f(k) of BTRS), j >= 0 whole
-static __device__ const float NMX_STIRLING_TAIL[10] = {
-    0.08106146679532726f, 0.04134069595540929f, 0.02767792568499834f, 0.02079067210376509f, 0.01664469118982119f,
-    0.01387612882307075f, 0.01189670994589177f, 0.01041126526197209f, 0.009255462182712733f, 0.008330563433362871f};
-
-__device__ __forceinline__ float nmx_stirling_tail(float j) {
-  if (j < 10.0f) return NMX_STIRLING_TAIL[(int)j];
-  const float r = 1.0f / (j + 1.0f), r2 = r * r;
-  return (1.0f / 12 - (1.0f / 360 - (1.0f / 1260) * r2) * r2) * r;
-}
-
 // Inlined like the other draws: k_program_predict keeps its occupancy (80 VGPRs, 6 waves / SIMD),
 // while the out-of-line form measured 106 VGPRs and 4 waves (DESIGN.md "Predictive programs").
-// lq is one live value where log q and log1p(-q) would be two: that register is the margin.
+// log((n - j + 1) q / ((j + 1) (1 - q))) is one log1p of ((n + 2) q - (j + 1)) / ((j + 1) (1 - q)) with
+// n q - j from one fmaf: as log((n - j + 1) / (j + 1)) + log(q / (1 - q)) the two logs cancel near the
+// mode and the quotient's rounding error, times j, reaches 1 at counts near 2^24.
+__device__ __forceinline__ float nmx_binomial_log_odds(float n, float q, float j) {
+  return log1pf((fmaf(n, q, -j) + (2.0f * q - 1.0f)) / ((j + 1.0f) * (1.0f - q)));
+}
+
 __device__ __forceinline__ float nmx_draw_binomial(float n, float p, uint64_t seed, uint32_t s, uint32_t stream,
                                                 uint32_t i) {
   if (!(p >= 0.0f && p <= 1.0f) || !(n >= 0.0f && n < NMX_BINOMIAL_MAX_COUNT) || n != floorf(n)) return NAN;
@@ -406,12 +419,12 @@ __device__ __forceinline__ float nmx_draw_binomial(float n, float p, uint64_t se
     }
     return NAN;
   }
-  const float lq = logf(q) - log1_q, spq = sqrtf(mu * (1.0f - q)), c = mu + 0.5f;
+  const float spq = sqrtf(mu * (1.0f - q)), c = mu + 0.5f;
   const float b = 1.15f + 2.53f * spq, a = -0.0873f + 0.0248f * b + 0.01f * q;
   const float alpha = (2.83f + 5.1f / b) * spq, v_r = 0.92f - 4.2f / b;
   const float m = floorf((n + 1.0f) * q);
-  const float log_h = (m + 0.5f) * (logf((m + 1.0f) / (n - m + 1.0f)) - lq) +
-                      (nmx_stirling_tail(m) + nmx_stirling_tail(n - m));
+  const float log_h =
+      (nmx_stirling_tail(m) + nmx_stirling_tail(n - m)) - (m + 0.5f) * nmx_binomial_log_odds(n, q, m);
   for (uint32_t t = 0; t < NMX_DRAW_MAX_ATTEMPTS; ++t) {
     const nmx_u4 w = nmx_rng(seed, s, stream, NMX_EV_PREDICT, i, t);
     const float U = nmx_u01(w.x) - 0.5f, V = nmx_u01_open0(w.y);
@@ -420,7 +433,7 @@ __device__ __forceinline__ float nmx_draw_binomial(float n, float p, uint64_t se
     if (us >= 0.07f && V <= v_r) return mirror ? n - k : k;
     if (!(k >= 0.0f && k <= n)) continue;
     const float log_f = (n + 1.0f) * log1pf((k - m) / (n - k + 1.0f)) +
-                        (k + 0.5f) * (logf((n - k + 1.0f) / (k + 1.0f)) + lq) +
+                        (k + 0.5f) * nmx_binomial_log_odds(n, q, k) +
                         (nmx_stirling_tail(k) - nmx_stirling_tail(n - k)) + log_h;
     if (logf(V * alpha / (a / (us * us) + b)) <= log_f) return mirror ? n - k : k;
   }

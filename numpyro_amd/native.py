@@ -121,6 +121,7 @@ DRAW_OPCODE = {n: DRAW_BASE + i for i, n in enumerate(DRAW_OPCODES)}
 DRAW_MAX_ATTEMPTS = 64  # NMX_DRAW_MAX_ATTEMPTS
 POISSON_MAX_STEPS = 96  # NMX_POISSON_MAX_STEPS
 POISSON_PTRS_RATE = 10.0  # NMX_POISSON_PTRS_RATE
+POISSON_MAX_RATE = 1 << 24  # NMX_POISSON_MAX_RATE
 BINOMIAL_MAX_STEPS = 96  # NMX_BINOMIAL_MAX_STEPS
 BINOMIAL_BTRS_MEAN = 10.0  # NMX_BINOMIAL_BTRS_MEAN
 BINOMIAL_MAX_COUNT = 1 << 24  # NMX_BINOMIAL_MAX_COUNT

@@ -84,7 +84,10 @@ def _dr_bernoulli_probs(B, d, n):
 
 
 def _dr_poisson(B, d, n):
-    return B.draw("draw_poisson", n, d["rate"])
+    rate = d["rate"]
+    if rate.is_const and np.any(rate.c >= native.POISSON_MAX_RATE):
+        raise NotImplementedError(f"a rate of {rate.c.max():g} (2^24 or more: counts are float32 whole numbers)")
+    return B.draw("draw_poisson", n, rate)
 
 
 def _dr_uniform(B, d, n):
@@ -346,8 +349,9 @@ def _host_gamma(a, blocks, T):
 
 
 def _host_poisson(rate, blocks, T):
-    """rate < 10: inversion of one uniform; else Hoermann's PTRS (1993), one block per attempt."""
-    ok = (rate >= 0) & np.isfinite(rate)
+    """rate < 10: inversion of one uniform; else Hoermann's PTRS (1993), one block per attempt;
+    NaN before any loop unless 0 <= rate < NMX_POISSON_MAX_RATE."""
+    ok = (rate >= 0) & (rate < T(native.POISSON_MAX_RATE))
     out = np.full(rate.shape, np.nan, T)
     att = np.full(rate.shape, -1, np.int32)
     zero = ok & (rate == 0)
@@ -373,7 +377,6 @@ def _host_poisson(rate, blocks, T):
             pending &= ~done
     pending = ok & (rate >= T(native.POISSON_PTRS_RATE))
     if pending.any():
-        log_rate = np.log(rate)
         b = T(0.931) + T(2.53) * np.sqrt(rate)
         a = T(-0.059) + T(0.02483) * b
         inv_alpha = T(1.1239) + T(1.1328) / (b - T(3.4))
@@ -388,7 +391,12 @@ def _host_poisson(rate, blocks, T):
             k = np.floor((T(2.0) * a / us + b) * U + rate + T(0.43))
             fast = (us >= T(0.07)) & (V <= v_r)
             rej = ~(k >= 0) | ((us < T(0.013)) & (V > us))
-            slow = np.log(V * inv_alpha / (a / (us * us) + b)) <= -rate + k * log_rate - _lgamma(k + T(1.0), T)
+            # log pmf(k) = -rate + k log rate - log k! with log k! as the Stirling formula at k + 1 plus
+            # its tail: the terms of size k log k cancel inside the log1p, not in the sum
+            k1 = np.where(k >= 0, k, T(0.0)) + T(1.0)
+            log_pmf = k * np.log1p((rate - k1) / k1) - (rate - k1) - T(0.5) * np.log(k1) - \
+                T(0.9189385332046727) - _stirling_tail(k1 - T(1.0), T)
+            slow = np.log(V * inv_alpha / (a / (us * us) + b)) <= log_pmf
             acc = pending & (fast | (~rej & slow))
             out[acc], att[acc] = k[acc], t
             pending &= ~acc
@@ -408,6 +416,13 @@ def _stirling_tail(j, T):
     r2 = r * r
     series = (T(1.0) / T(12) - (T(1.0) / T(360) - (T(1.0) / T(1260)) * r2) * r2) * r
     return np.where(small, table[np.where(small, j, 0).astype(np.int64)], series)
+
+
+def _fma(x, y, z, T):
+    """x y + z rounded once (fmaf): two float32 factors have an exact float64 product."""
+    if T is np.float32:
+        return (x.astype(np.float64) * y.astype(np.float64) + np.asarray(z, np.float64)).astype(np.float32)
+    return x * y + z
 
 
 def _host_binomial(n, p, blocks, T, steps=None):
@@ -455,14 +470,18 @@ def _host_binomial(n, p, blocks, T, steps=None):
             pending &= ~done
     pending = live & ~small
     if pending.any():
-        lq = np.log(q) - log1_q
         spq, c = np.sqrt(mu * (T(1.0) - q)), mu + T(0.5)
         b = T(1.15) + T(2.53) * spq
         a = T(-0.0873) + T(0.0248) * b + T(0.01) * q
         alpha, v_r = (T(2.83) + T(5.1) / b) * spq, T(0.92) - T(4.2) / b
         m = np.floor((nn + T(1.0)) * q)
-        log_h = (m + T(0.5)) * (np.log((m + T(1.0)) / (nn - m + T(1.0))) - lq) + \
-            (_stirling_tail(m, T) + _stirling_tail(nn - m, T))
+
+        def log_odds(j):
+            # log((n - j + 1) q / ((j + 1) (1 - q))) as the log1p of ((n + 2) q - (j + 1)) / ((j + 1) (1 - q)):
+            # n q - j is one fused multiply-add, rounded once, where the two logs would cancel
+            return np.log1p((_fma(nn, q, -j, T) + (T(2.0) * q - T(1.0))) / ((j + T(1.0)) * (T(1.0) - q)))
+
+        log_h = (_stirling_tail(m, T) + _stirling_tail(nn - m, T)) - (m + T(0.5)) * log_odds(m)
         for t in range(native.DRAW_MAX_ATTEMPTS):
             if not pending.any():
                 break
@@ -475,7 +494,7 @@ def _host_binomial(n, p, blocks, T, steps=None):
             inside = (k >= 0) & (k <= nn)
             kk = np.where(inside, k, m)
             log_f = (nn + T(1.0)) * np.log1p((kk - m) / (nn - kk + T(1.0))) + \
-                (kk + T(0.5)) * (np.log((nn - kk + T(1.0)) / (kk + T(1.0))) + lq) + \
+                (kk + T(0.5)) * log_odds(kk) + \
                 (_stirling_tail(kk, T) - _stirling_tail(nn - kk, T)) + log_h
             slow = np.log(V * alpha / (a / (us * us) + b)) <= log_f
             acc = pending & (fast | (inside & slow))

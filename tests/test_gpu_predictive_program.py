@@ -199,13 +199,18 @@ def test_out_of_support_inputs_give_nan_and_touch_nothing_else(device):
     rs = np.random.RandomState(2)
     X = rs.randn(70, 3)
     good = {"sigma_a": (0.5 + np.abs(rs.randn(6))).astype(np.float32), "b": (0.5 * rs.randn(6, 3)).astype(np.float32)}
+    # a seventh sample whose rates are all at or above NMX_POISSON_MAX_RATE in the bad inputs
+    good = {"sigma_a": np.append(good["sigma_a"], np.float32(1.0)),
+            "b": np.vstack([good["b"], np.zeros((1, 3), np.float32)])}
     bad = {k: v.copy() for k, v in good.items()}
     bad["sigma_a"][1] = -1.0
     bad["b"][4, 0] = np.nan
+    bad["sigma_a"][6] = 2.0 ** 24
     ref = _np(Predictive(model, _torch(good))(8, X))
     out = _np(Predictive(model, _torch(bad))(8, X))
     assert np.all(np.isfinite(ref["g"])) and ref["y"].min() >= 0
     assert np.all(np.isnan(out["g"][1])) and np.all(out["y"][1] == -1) and np.all(out["y"][4] == -1)
+    assert np.all(out["y"][6] == -1) and np.all(np.isfinite(out["g"][6]))
     assert np.array_equal(out["g"][4], ref["g"][4])  # the NaN coefficient does not reach g
     others = [0, 2, 3, 5]
     for site in ("g", "y"):

@@ -339,11 +339,19 @@ def test_out_of_support_parameters_give_nan_without_looping():
             numpyro.sample("b", dist.Bernoulli(probs=c))
 
     prog = compile_predictive(model, (), {}, ["c"])
-    out = prog.run_host({"c": np.array([0.5, -1.0, np.nan, np.inf, 0.0])}, 1, PC.words)
+    info = {}
+    out = prog.run_host({"c": np.array([0.5, -1.0, np.nan, np.inf, 0.0, 2.0 ** 24, 2.0 ** 24 - 1])}, 1, PC.words,
+                        info=info)
     for name in ("g", "k", "k_small", "b"):
         assert np.all(np.isfinite(out[name][0])), name
         assert np.all(np.isnan(out[name][1:4])), name  # negative, NaN, infinite
     assert np.all(np.isnan(out["g"][4])) and np.all(out["k"][4] == 0) and np.all(out["b"][4] == 0)
+    # NMX_POISSON_MAX_RATE: a rate of 2^24 or more is refused before any loop, the rate below it is drawn
+    (stream,) = [o for o in prog.outputs if o.name == "k_small"][0].streams
+    assert np.all(np.isnan(out["k"][5:])) and np.all(np.isnan(out["k_small"][5])) and np.all(info[stream][5] == -1)
+    assert np.all(np.isfinite(out["k_small"][6])) and np.all(np.abs(out["k_small"][6] - 2.0 ** 24) < 6 * 2.0 ** 12)
+    with pytest.raises(NotImplementedError, match="site 'k'.*rate"):
+        compile_predictive(lambda: numpyro.sample("k", dist.Poisson(2.0 ** 24)), (), {}, [])
 
 
 @pytest.fixture(scope="module")
