@@ -48,6 +48,9 @@ def fixed_step_case(model, dim, rs):
         return (mu, sd), P.diag_normal, OP.IsoNormal(mu, sd, dtype=np.float32), "x", (lambda z: z), 0.05, 0.95, None
     if model == "funnel":
         return (dim,), P.funnel, OP.Funnel(dim, dtype=np.float32), "x", (lambda z: z[..., :-1]), 0.05, 0.9, None
+    if model == "funnel_reparam":
+        return (dim,), P.funnel_reparam, OP.FunnelNonCentered(dim, dtype=np.float32), "x_decentered", \
+            (lambda z: z[..., :-1]), 0.3, 0.95, None
     if model == "sv":
         r = datasets.sp500_synthetic(T=dim - 2)
         return (r,), P.stochastic_volatility, OP.StochasticVolatility(r, dtype=np.float32), "s", \
@@ -117,11 +120,12 @@ def traced(o, s, T):
     return hist
 
 
-def oracle_runs(pe_grad, dim, C, T, seed, step, z0, algo="NUTS", **kw):
-    """Fixed-step oracle chains from init_to_uniform (or the shared z0), traced."""
+def oracle_runs(pe_grad, dim, C, T, seed, step, z0, algo="NUTS", num_warmup=0, **kw):
+    """Fixed-step oracle chains from init_to_uniform (or the shared z0), traced.  `num_warmup`
+    transitions count as warmup (nothing adapts; max_tree_depth=(a, b) takes depth a there)."""
     hist = []
     for c in range(C):
-        o = H.NUTSOracle(pe_grad, dim, 0, algo=algo, step_size=step, adapt_step_size=False,
+        o = H.NUTSOracle(pe_grad, dim, num_warmup, algo=algo, step_size=step, adapt_step_size=False,
                          adapt_mass_matrix=False, **kw)
         zc = philox.init_uniform(seed, c, 0, dim) if z0 is None else z0[c]
         hist.append(traced(o, o.init(zc, seed, c), T))
@@ -130,7 +134,9 @@ def oracle_runs(pe_grad, dim, C, T, seed, step, z0, algo="NUTS", **kw):
 
 def as_trace(hist, L=1024):
     """An oracle run in the device's trace layout (oracle/parity.py oracle_to_trace): the second
-    side of a calibration comparison.  Returns (trace [T, C, L, 8], num_steps [C, T], z [C, T, D])."""
+    side of a calibration comparison; L leaves per transition, at least the largest tree (the device
+    trace has 1 << max depth: depth 12 needs 4096).  Returns (trace [T, C, L, 8], num_steps [C, T],
+    z [C, T, D])."""
     C, T = len(hist), min(len(h) for h in hist)
     tr = np.full((T, C, L, 8), np.nan, np.float32)
     ns = np.zeros((C, T), np.int64)
@@ -174,20 +180,27 @@ def report(par, label, cal=None, frac=None):
 
 
 def engine_fixed(model, dim, C, T, seed, k, trace=True, dense_matrix=None, max_tree_depth=10, algo="NUTS",
-                 **extra):
+                 num_warmup=0, max_delta_energy=None, case=None, step=None, **extra):
     """A fixed-step engine run of the case (trace of the first k chains on): (engine, oracle
     potential, step, min match, z0, num_steps [C, T], draws [C, T, D] (model space,
-    constrained), samples, fields)."""
+    constrained), samples, fields).  `num_warmup` of the T transitions count as warmup (nothing
+    adapts; they are collected like the others); `max_delta_energy` sets the engine's divergence
+    threshold (SamplerOptions.max_delta_energy: the kernels take no such argument, like the
+    reference's); `case` is a fixed_step_case tuple used instead of the (model, dim) one, `step`
+    a step size instead of the case's."""
     rs = np.random.RandomState(dim)
-    args, fm, ref, site, extract, step, frac, z0 = fixed_step_case(model, dim, rs)
+    args, fm, ref, site, extract, step0, frac, z0 = fixed_step_case(model, dim, rs) if case is None else case
+    step = step0 if step is None else step
     kw = dict(step_size=step, adapt_step_size=False, adapt_mass_matrix=False, **extra)
     if algo == "NUTS":
         kw["max_tree_depth"] = max_tree_depth
     if dense_matrix is not None:
         kw.update(dense_mass=True, inverse_mass_matrix=dense_matrix)
     eng = (NUTS if algo == "NUTS" else HMC)(fm, **kw).make_engine(C, args)
+    if max_delta_energy is not None:
+        eng.opts.max_delta_energy = float(max_delta_energy)
     ip = None if z0 is None else torch.from_numpy(z0[:C])
-    eng.initialize(seed, 0, init_params=ip)
+    eng.initialize(seed, num_warmup, init_params=ip)
     if trace:
         eng.set_trace(k, 0, T)
     samples, fields, _ = eng.run(T, seed)
