@@ -29,6 +29,7 @@
 
 #include "nmx_api_internal.h"
 #include "nmx_common.h"
+#include "x3_sched.h"
 
 namespace {
 
@@ -331,6 +332,21 @@ __device__ __forceinline__ void x3_labels_wait(f32x4 (&y4)[4]) {
   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(y4[0]), "+v"(y4[1]), "+v"(y4[2]), "+v"(y4[3]));
 }
 
+// the same in halves (y4[2 HALF], y4[2 HALF + 1]) off one address register: x3_item SCHED 1 reads
+// the second half late
+template <int HALF>
+__device__ __forceinline__ void x3_labels_half(const char* ybase, int h, f32x4& ya, f32x4& yb) {
+  const unsigned a = (unsigned)(size_t)((__attribute__((address_space(3))) const char*)ybase) + 64 * h;
+  asm volatile(
+      "ds_read_b128 %0, %2 offset:%3\n\t"
+      "ds_read_b128 %1, %2 offset:%4"
+      : "=&v"(ya), "=&v"(yb)
+      : "v"(a), "i"(32 * HALF), "i"(32 * HALF + 16));
+}
+__device__ __forceinline__ void x3_labels_half_wait(f32x4& ya, f32x4& yb) {
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ya), "+v"(yb));
+}
+
 // Bernoulli-logits epilogue on the GEMM1 accumulator, rows 2p and 2p+1 (no row mask: padded
 // rows have l = 0 and zero X).  The accumulator holds m = -l log2(e) (Z pre-scaled by -log2 e
 // before its split), so e = 2^-|m| needs no multiply and sum |l| = ln 2 sum |m|.
@@ -572,6 +588,135 @@ inline size_t x3_lds_bytes() {
 }
 
 
+// ---------------------------------------------------------------------------------------
+// SCHED 1: the main form's tile step hand-placed (x3_sched.h makes the placement).
+//
+// One wave issues in order, and an MFMA hides at most 24 issue cycles behind it.  SCHED 0 leaves
+// the order to the compiler under igrouplp hints: it packs tile k's epilogue into the first
+// GEMM1(k+1) gaps, puts most of the first split half in a lump between the two GEMMs and runs
+// GEMM2's last ten MFMAs bare.  Here every MFMA of GEMM1(k+1) and GEMM2(k) is written out with its
+// fillers behind it and __builtin_amdgcn_sched_barrier(0) after them, as in x3_a_tile, and the
+// epilogue is rotated across the tile boundary: GEMM2(k)'s gaps, which of tile k can only take
+// the second split half and the U term, get the label-free part (x3_epi_one without its last
+// add) of the first NMX_X3_ROT values of tile k+1, whose GEMM1 accumulator is complete by then;
+// their labels (the B slot of tile k+1 lands a step later) are added beside GEMM1(k+2), with
+// the rest of that epilogue and the first split half.
+//
+// Every value sees x3_epi_one's operations on the same operands in the same order (the running
+// sum of |m| and the two products in value order), split3's per pair, x3_epi_finish once per
+// tile in tile order, and every accumulator x3_gemm1's / x3_gemm2's products in their order:
+// bitwise the results of SCHED 0 and of the tail forms.
+// ---------------------------------------------------------------------------------------
+#ifndef NMX_X3_SCHED
+#define NMX_X3_SCHED 1
+#endif
+#ifndef NMX_X3_ROT
+#define NMX_X3_ROT 6
+#endif
+// the first split half starts in this gap of GEMM1(k+1) (x3s::plan1)
+#ifndef NMX_X3_SPLIT_FROM
+#define NMX_X3_SPLIT_FROM 8
+#endif
+// the rotated operations start in this gap of GEMM2(k) (x3s::plan2)
+#ifndef NMX_X3_ROT_FROM
+#define NMX_X3_ROT_FROM 12
+#endif
+// the labels of the tile's rows 8..15 are read in gap NMX_X3_LAB_HI - 2 of GEMM1(k+1) and waited
+// for at the start of gap NMX_X3_LAB_HI (their eight registers are not live before)
+#ifndef NMX_X3_LAB_HI
+#define NMX_X3_LAB_HI 4
+#endif
+// an operand fragment is read this many MFMAs ahead of its first use
+#ifndef NMX_X3_LEAD
+#define NMX_X3_LEAD 2
+#endif
+
+// the lane's index in its wave from the execution mask, behind an empty asm the compiler cannot
+// see through: a value to compute after the tile loop instead of keeping it in a register
+__device__ __forceinline__ int x3_lane_again() {
+  unsigned zero = 0;
+  asm volatile("" : "+v"(zero));
+  return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero));
+}
+
+template <int B, int E, class F>
+__device__ __forceinline__ void x3_static_for(F&& f) {
+  if constexpr (B < E) {
+    f(std::integral_constant<int, B>{});
+    x3_static_for<B + 1, E>(f);
+  }
+}
+
+// the label-free state of a tile's epilogue: copysign(1/(1+e) - 1/2, m) per value, sum |m|, the
+// two products of 1 + e
+struct x3_epi_state {
+  float sg[16];
+  float lin;
+  float prod[2];
+};
+// values between two operations of a value's epilogue / of a pair's split
+struct x3_epi_tmp {
+  float ope[16], h[16];
+};
+struct x3_split_state {
+  unsigned u[2][3][4];  // [half][term][pair]: split3's w1, w2, w3
+  float e[2][4][2], f[2][4][2];
+  float hl, lg;  // the U term's f32 parts
+};
+
+// one operation of the placement (x3s::Kind); x3_epi_one, split3's loop body and x3_epi_term /
+// x3_epi_finish cut at their instructions
+template <int KIND, int ARG>
+__device__ __forceinline__ void x3_op(const f32x16& acc, x3_epi_state& st, x3_epi_tmp& tmp, const f32x4 (&y4)[4],
+                                      float (&res)[16], x3_split_state& sp, double& pe) {
+  constexpr int v = ARG & 15;                  // epilogue operations: the value
+  constexpr int hf = (ARG >> 2) & 1, p = ARG & 3;  // split operations: half, pair
+  constexpr int r0 = 8 * hf + 2 * p, r1 = r0 + 1;
+  if constexpr (KIND == x3s::EXP) tmp.ope[v] = __builtin_amdgcn_exp2f(-fabsf(acc[v]));
+  else if constexpr (KIND == x3s::ONE) tmp.ope[v] = tmp.ope[v] + 1.0f;
+  else if constexpr (KIND == x3s::PROD) st.prod[v & 1] = st.prod[v & 1] * tmp.ope[v];
+  else if constexpr (KIND == x3s::LIN) st.lin += fabsf(acc[v]);
+  else if constexpr (KIND == x3s::RCP) tmp.h[v] = __builtin_amdgcn_rcpf(tmp.ope[v]);
+  else if constexpr (KIND == x3s::HALF) tmp.h[v] = tmp.h[v] - 0.5f;
+  else if constexpr (KIND == x3s::SIGN) st.sg[v] = __builtin_copysignf(tmp.h[v], acc[v]);  // x3_epi_one's bit insert
+  else if constexpr (KIND == x3s::LAB) res[v] = st.sg[v] + y4[v >> 2][v & 3];
+  else if constexpr (KIND == x3s::U1) sp.u[hf][0][p] = pk_bf16(res[r0], res[r1]);
+  else if constexpr (KIND == x3s::E0) sp.e[hf][p][0] = res[r0] - pk_lo(sp.u[hf][0][p]);
+  else if constexpr (KIND == x3s::E1) sp.e[hf][p][1] = res[r1] - pk_hi(sp.u[hf][0][p]);
+  else if constexpr (KIND == x3s::U2) sp.u[hf][1][p] = pk_bf16(sp.e[hf][p][0], sp.e[hf][p][1]);
+  else if constexpr (KIND == x3s::F0) sp.f[hf][p][0] = sp.e[hf][p][0] - pk_lo(sp.u[hf][1][p]);
+  else if constexpr (KIND == x3s::F1) sp.f[hf][p][1] = sp.e[hf][p][1] - pk_hi(sp.u[hf][1][p]);
+  else if constexpr (KIND == x3s::U3) sp.u[hf][2][p] = pk_bf16(sp.f[hf][p][0], sp.f[hf][p][1]);
+  else if constexpr (KIND == x3s::FINA) {
+    sp.hl = 0.5f * st.lin;
+    sp.lg = __builtin_amdgcn_logf(st.prod[0] * st.prod[1]);
+  } else {
+    static_assert(KIND == x3s::FINB, "x3_op: unknown operation");
+    pe += (double)sp.hl * (double)LN2 + (double)sp.lg * (double)LN2;
+  }
+}
+
+// the fillers of gap G of a plan
+template <const x3s::Plan& PL, int G>
+__device__ __forceinline__ void x3_fill(const f32x16& acc, x3_epi_state& st, x3_epi_tmp& tmp, const f32x4 (&y4)[4],
+                                        float (&res)[16], x3_split_state& sp, double& pe) {
+  x3_static_for<0, PL.n[G]>([&](auto Q) {
+    constexpr x3s::Op o = PL.op[G][decltype(Q)::value];
+    x3_op<o.kind, o.arg>(acc, st, tmp, y4, res, sp, pe);
+  });
+}
+
+// the operands of MFMA i of a group of six (x3_gemm1's / x3_gemm2's order): the A plane
+// (a3, a2, a1, a2, a1, a1) and the B term (1, 2, 3, 1, 2, 1), zero-based
+constexpr int x3_six_a(int i) { return i == 0 ? 2 : (i == 1 || i == 3) ? 1 : 0; }
+constexpr int x3_six_b(int i) { return (i == 0 || i == 3 || i == 5) ? 0 : (i == 1 || i == 4) ? 1 : 2; }
+
+template <int ROT, int NG>
+inline constexpr x3s::Plan x3_plan1 = x3s::plan1(ROT, NG, NMX_X3_SPLIT_FROM < NG ? NMX_X3_SPLIT_FROM : NG - 1, NMX_X3_LAB_HI);
+template <int ROT, int NG, int DT>
+inline constexpr x3s::Plan x3_plan2 = x3s::plan2(ROT, NG, 6 * DT, NMX_X3_ROT_FROM);
+
+
 template <int KB, int DT, int H, int SCHED>
 __device__ __forceinline__ void x3_item(const char* __restrict__ Xq, int64_t ntiles, int D, int S, int split, int ct,
                                         nmx_eval_batch ev, float* __restrict__ gpart,
@@ -662,6 +807,184 @@ __device__ __forceinline__ void x3_item(const char* __restrict__ Xq, int64_t nti
       issue_b(0);
       f32x16 accA, accB;
       if (active) accA = x3_gemm1<KB, H, CMP>(reinterpret_cast<const bf16x8*>(aring) + lane, z1, z2, z3);
+      if constexpr (SCHED == 1) {
+        static_assert(!TR, "SCHED 1 reads GEMM2's operand from the B ring");
+        constexpr int ROT = NMX_X3_ROT, LEAD = NMX_X3_LEAD;
+        constexpr int NM1 = 6 * (KB - H) + 3 * H, NM2 = 12 * DT;  // MFMAs of GEMM1, GEMM2
+        static_assert(ROT >= 0 && ROT <= 16 && LEAD >= 1 && LEAD <= NM1 && NM1 <= x3s::MAXG && NM2 <= x3s::MAXG, "plan");
+        // A fragment (kb, pl) of GEMM1 -- with H the last k-block holds the combined pieces c0, c1
+        // as pl = 0, 1 -- and B fragment (group = s DT + dt, pl) of GEMM2: first used by MFMA
+        // 6 kb + 2 - pl (x3_six_a; the combined c1 by 6 (KB - 1), c0 one later), read LEAD MFMAs
+        // before that; phase 2's first reads lie in phase 1's last gaps
+        struct use {
+          static constexpr int a(int kb, int pl) { return (H && kb == KB - 1) ? 6 * kb + 1 - pl : 6 * kb + 2 - pl; }
+          static constexpr int b(int gi, int pl) { return 6 * gi + 2 - pl; }
+        };
+        x3_epi_state stA, stB;
+        // the label-free part of the first ROT values, not overlapped (the split's first tile)
+        auto rotate_bare = [&](const f32x16& acc, x3_epi_state& st) {
+          st.lin = 0.0f;
+          st.prod[0] = st.prod[1] = 1.0f;
+          x3_epi_tmp tmp;
+          f32x4 y4[4];
+          float res[16];
+          x3_split_state sp;
+          x3_static_for<0, ROT>([&](auto V) {
+            constexpr int v = decltype(V)::value;
+            x3_op<x3s::EXP, v>(acc, st, tmp, y4, res, sp, pe);
+            x3_op<x3s::ONE, v>(acc, st, tmp, y4, res, sp, pe);
+            x3_op<x3s::PROD, v>(acc, st, tmp, y4, res, sp, pe);
+            x3_op<x3s::LIN, v>(acc, st, tmp, y4, res, sp, pe);
+            x3_op<x3s::RCP, v>(acc, st, tmp, y4, res, sp, pe);
+            x3_op<x3s::HALF, v>(acc, st, tmp, y4, res, sp, pe);
+            x3_op<x3s::SIGN, v>(acc, st, tmp, y4, res, sp, pe);
+          });
+        };
+        if (active) rotate_bare(accA, stA);
+        // one tile that has a successor: the rest of tile k's epilogue (`acc`, `st`) and the
+        // first split half beside GEMM1 of tile k+1 into `nxt`, then GEMM2 of tile k with the
+        // second split half, the U term and the start of tile k+1's epilogue (`nst`)
+        auto step = [&](auto PARC, int k, const f32x16& acc, x3_epi_state& st, f32x16& nxt, x3_epi_state& nst) {
+          constexpr int PAR = decltype(PARC)::value;  // k & 1: the ring slots are compile-time offsets
+          static_assert(ASL == 2, "two A slots");
+          static_assert(x3_plan1<ROT, NM1>.ok && x3_plan2<ROT, NM2, DT>.ok, "SCHED 1: the placement is incomplete");
+          x3_wait_vm<0>();
+          asm volatile("s_barrier" ::: "memory");
+          if (k + 2 < nt) issue_a(k + 2);
+          issue_b(k + 1);
+          if (!active) return;
+          const char* bs = bring + PAR * BSZ * 1024;
+          constexpr int LABHI = NMX_X3_LAB_HI;
+          static_assert(LABHI >= 2 && LABHI < NM1, "the second label half is read inside phase 1");
+          f32x4 y4[4];
+          x3_labels_half<0>(bs + (BSZ - 1) * 1024, h, y4[0], y4[1]);
+          const bf16x8* fa = reinterpret_cast<const bf16x8*>(aring + (1 - PAR) * NAL * 1024) + lane;
+          const bf16x8* fbp = reinterpret_cast<const bf16x8*>(bs) - NA * 64 + lane;
+          bf16x8 af[KB][3], bf[2 * DT][3];
+          auto read_a = [&](auto J) {  // the A fragments whose read lies in gap J (J < 0: before the phase)
+            constexpr int j = decltype(J)::value;
+            x3_static_for<0, KB>([&](auto KBI) {
+              constexpr int kb = decltype(KBI)::value;
+              x3_static_for<0, (H && kb == KB - 1) ? 2 : 3>([&](auto PLI) {
+                constexpr int pl = decltype(PLI)::value;
+                constexpr int at = use::a(kb, pl) - LEAD;
+                if constexpr (j < 0 ? at < 0 : at == j)
+                  af[kb][pl] = fa[((H && kb == KB - 1) ? x3_ci<KB, CMP>(pl) : x3_ai<KB, CMP>(pl, kb)) * 64];
+              });
+            });
+          };
+          auto read_b = [&](auto J) {  // the B fragments whose read lies in gap J of phase 2 (J < 0: phase 1's NM1 + J)
+            constexpr int j = decltype(J)::value;
+            x3_static_for<0, 2 * DT>([&](auto GI) {
+              constexpr int gi = decltype(GI)::value, s = gi / DT, dt = gi % DT;
+              x3_static_for<0, 3>([&](auto PLI) {
+                constexpr int pl = decltype(PLI)::value;
+                if constexpr (use::b(gi, pl) - LEAD == j) bf[gi][pl] = fbp[(NA + pl * 2 * DT + 2 * dt + s) * 64];
+              });
+            });
+          };
+          read_a(std::integral_constant<int, -1>{});
+          x3_labels_half_wait(y4[0], y4[1]);
+          __builtin_amdgcn_sched_barrier(0);
+          x3_epi_tmp tmp, ntmp;
+          x3_split_state sp;
+          float res[16];
+          // phase 1: GEMM1(k+1), product order of x3_gemm1
+#pragma unroll
+          for (int r = 0; r < 16; ++r) nxt[r] = 0.0f;
+          x3_static_for<0, NM1>([&](auto J) {
+            constexpr int j = decltype(J)::value;
+            constexpr int kb = j / 6 < KB - H ? j / 6 : KB - 1, i = j - 6 * kb;
+            if constexpr (H && kb == KB - 1) {  // (c1, z3), (c0, z2), (c0, z1)
+              nxt = x3_mma(af[kb][i == 0 ? 1 : 0], i == 0 ? z3[kb] : (i == 1 ? z2[kb] : z1[kb]), nxt);
+            } else {
+              constexpr int b = x3_six_b(i);
+              nxt = x3_mma(af[kb][x3_six_a(i)], b == 0 ? z1[kb] : (b == 1 ? z2[kb] : z3[kb]), nxt);
+            }
+            if constexpr (j == LABHI) x3_labels_half_wait(y4[2], y4[3]);
+            read_a(J);
+            read_b(std::integral_constant<int, j - NM1>{});
+            if constexpr (j == LABHI - 2) x3_labels_half<1>(bs + (BSZ - 1) * 1024, h, y4[2], y4[3]);
+            x3_fill<x3_plan1<ROT, NM1>, j>(acc, st, tmp, y4, res, sp, pe);
+            __builtin_amdgcn_sched_barrier(0);
+          });
+          // phase 2: GEMM2(k), product order of x3_gemm2
+          nst.lin = 0.0f;
+          nst.prod[0] = nst.prod[1] = 1.0f;
+          x3_static_for<0, NM2>([&](auto J) {
+            constexpr int j = decltype(J)::value, gi = j / 6, i = j % 6, s = gi / DT, dt = gi % DT;
+            const bf16x8 r = __builtin_bit_cast(
+                bf16x8, (u32x4){sp.u[s][x3_six_b(i)][0], sp.u[s][x3_six_b(i)][1], sp.u[s][x3_six_b(i)][2],
+                                sp.u[s][x3_six_b(i)][3]});
+            g[dt] = x3_mma(bf[gi][x3_six_a(i)], r, g[dt]);
+            read_b(J);
+            // rotated operations work on tile k+1 (`nxt`); the split and the U term on tile k
+            x3_static_for<0, x3_plan2<ROT, NM2, DT>.n[j]>([&](auto Q) {
+              constexpr x3s::Op o = x3_plan2<ROT, NM2, DT>.op[j][decltype(Q)::value];
+              if constexpr (o.kind <= x3s::SIGN) x3_op<o.kind, o.arg>(nxt, nst, ntmp, y4, res, sp, pe);
+              else x3_op<o.kind, o.arg>(acc, st, tmp, y4, res, sp, pe);
+            });
+            __builtin_amdgcn_sched_barrier(0);
+          });
+        };
+        // the split's last tile (once per workgroup): no GEMM1 -- SCHED 0 runs it on a stale slot
+        // and drops the result -- and nothing to rotate; the order is left to the compiler
+        auto last = [&](int k, const f32x16& acc, x3_epi_state& st) {
+          x3_wait_vm<0>();
+          asm volatile("s_barrier" ::: "memory");
+          if (!active) return;
+          // lane and h computed again (see the stores below the loop)
+          const int lane = x3_lane_again(), h = lane >> 5;
+          const char* bs = bring + (k & 1) * BSZ * 1024;
+          f32x4 y4[4];
+          x3_labels(bs + (BSZ - 1) * 1024, h, y4);
+          x3_labels_wait(y4);
+          float res[16];
+#pragma unroll
+          for (int v = 0; v < 16; ++v) {
+            if (v < ROT) res[v] = st.sg[v] + y4[v >> 2][v & 3];
+            else x3_epi_one(acc[v], y4[v >> 2][v & 3], res[v], st.lin, st.prod[v & 1]);
+          }
+          x3_epi_finish(st.lin, st.prod, pe);
+          // x3_gemm2 with its operand reads pinned beside their MFMAs (left free, the compiler reads
+          // all twelve fragments ahead and the registers they take spill the Z fragments kernel-wide)
+          const bf16x8* fbp = reinterpret_cast<const bf16x8*>(bs) - NA * 64 + lane;
+#pragma unroll
+          for (int s = 0; s < 2; ++s) {
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = res[8 * s + j];
+            bf16x8 r1, r2, r3;
+            split3(v, r1, r2, r3);
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) {
+              __builtin_amdgcn_sched_barrier(0);
+              const bf16x8 b1 = fbp[(NA + 0 * 2 * DT + 2 * dt + s) * 64];
+              const bf16x8 b2 = fbp[(NA + 1 * 2 * DT + 2 * dt + s) * 64];
+              const bf16x8 b3 = fbp[(NA + 2 * 2 * DT + 2 * dt + s) * 64];
+              g[dt] = x3_mma(b3, r1, g[dt]);
+              g[dt] = x3_mma(b2, r2, g[dt]);
+              g[dt] = x3_mma(b1, r3, g[dt]);
+              g[dt] = x3_mma(b2, r1, g[dt]);
+              g[dt] = x3_mma(b1, r2, g[dt]);
+              g[dt] = x3_mma(b1, r1, g[dt]);
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        };
+        // tiles 0 .. nt - 2 with the two accumulators alternating, then the last (one copy of its
+        // code: the accumulator and state it ends on are moved, once per workgroup)
+        for (int k = 0; k < nt - 1; k += 2) {
+          step(std::integral_constant<int, 0>{}, k, accA, stA, accB, stB);
+          if (k + 1 < nt - 1) {
+            step(std::integral_constant<int, 1>{}, k + 1, accB, stB, accA, stA);
+          } else {
+            accA = accB;
+            stA = stB;
+          }
+        }
+        last(nt - 1, accA, stA);
+      } else {
       // one tile: epilogue + GEMM2 of tile k on `acc`, GEMM1 of tile k+1 into `nxt`; the loop
       // below alternates the two accumulators (no register copy between tiles)
       auto step = [&](int k, const f32x16& acc, f32x16& nxt) {
@@ -706,7 +1029,26 @@ __device__ __forceinline__ void x3_item(const char* __restrict__ Xq, int64_t nti
         step(k, accA, accB);
         if (k + 1 < nt) step(k + 1, accB, accA);
       }
+      }  // SCHED 0
     }
+  }
+  if constexpr (SCHED == 1) {
+    // the store positions computed again: carried through the tile loop, the lane's index and what
+    // is derived from it were the registers that spilled
+    const int lane2 = x3_lane_again();
+    const int h2 = lane2 >> 5;
+    const int pos2 = (ct * 4 + wu) * 32 + (lane2 & 31);
+    if (!active || pos2 >= ldc) return;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int d = 32 * dt + (r & 3) + 8 * (r >> 2) + 4 * h2;
+        if (d < D) gpart[((size_t)split * D + d) * ldc + pos2] = g[dt][r];
+      }
+    const double p = pe + __shfl_xor(pe, 32);
+    if (h2 == 0) pepart[(size_t)split * ldc + pos2] = p;
+    return;
   }
   if (!active || pos >= ldc) return;
 #pragma unroll
@@ -1494,7 +1836,7 @@ extern "C" int nmx_logreg_pe_grad(const void* packed, int64_t n_rows, int dim, c
                          dim, S, Gt, *ev, gpart, pepart);
   }
   else if (KB == 4 && H)
-    hipLaunchKernelGGL((k_logreg_x3<4, 2, 1, 3, 0>), grid, blk, (x3_lds_bytes<4, 2, 1>()), s, Xq, nt, dim, S, Gt,
+    hipLaunchKernelGGL((k_logreg_x3<4, 2, 1, 3, NMX_X3_SCHED>), grid, blk, (x3_lds_bytes<4, 2, 1>()), s, Xq, nt, dim, S, Gt,
                        *ev, gpart, pepart);
   else if (KB == 4)
     hipLaunchKernelGGL((k_logreg_x3<4, 2, 0, 3, 0>), grid, blk, (x3_lds_bytes<4, 2, 0>()), s, Xq, nt, dim, S, Gt,
