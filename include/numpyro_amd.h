@@ -382,6 +382,21 @@ size_t nmx_pe_bnn_workspace_bytes(int Dx, int H, int num_chains);
  *     g_a[e] += g_dst[e / aux] exp(a[e] - dst[e / aux]).
  *   NMX_OP_CONCAT: dst[i] = a[i] for i < aux, b[i - aux] for aux <= i < n, 0 < aux < n; each
  *     operand is a slot value or a constant (~ref), at least one a slot.
+ *   NMX_OP_CHOLESKY: a is a slot value of n = aux * aux elements, an aux x aux matrix stored
+ *     row-major of which only the lower triangle is read; dst (n elements) is its lower
+ *     Cholesky factor L, the strict upper triangle exact zeros.  Column j is
+ *     L[i][j] = (A[i][j] - sum_{k < j} L[i][k] L[j][k]) / L[j][j], k ascending; a pivot that is
+ *     not positive and finite is NaN, and so is every element computed from it.  Adjoint: with
+ *     Lbar the adjoint of dst (its strict upper part is ignored) and Phi the lower triangle
+ *     with a halved diagonal, P = L^-T Phi(L^T Lbar) L^-1 and g_a += (P + P^T) / 2, the
+ *     symmetric convention; computed in place in dst's adjoint slots by the unblocked
+ *     level-2 reverse sweep (Murray 2016).  1 <= aux <= NMX_CHOL_MAX_N.
+ *   NMX_OP_TRISOLVE: dst = L^-1 b, n elements, by forward substitution (the updates of an
+ *     element in column order); a refers to L, n * n elements row-major of which the lower
+ *     triangle is read, b to the right-hand side, n elements; each is a slot value or a constant
+ *     (~ref), at least one a slot.  Adjoint: w = L^-T g_dst by back substitution, g_b += w,
+ *     g_a[i][j] -= w[i] dst[j] for j <= i, each only where the operand is a slot.
+ *     1 <= n <= NMX_CHOL_MAX_N.
  * Sums run in an order fixed by the program alone (per-lane strided partial sums, then a
  * fixed butterfly over the 64 lanes), with no atomics: U and the gradient are bitwise
  * independent of chain count, position, ldc, list order. ---- */
@@ -393,6 +408,14 @@ enum nmx_opcode {
   NMX_OP_CUMSUM, NMX_OP_LOGSUMEXP, NMX_OP_CONCAT,                       /* read across elements, like the row above */
   NMX_NUM_OPCODES
 };
+/* The dense linear-algebra ops: arithmetic ops that read across elements like the last rows of
+ * nmx_opcode, numbered apart from them (after NMX_OP_CONCAT, before the draw ops).  One wave owns
+ * a chain and a matrix is n * n slots plus as many adjoints, hence the cap on n. */
+enum nmx_linalg_opcode {
+  NMX_OP_CHOLESKY = 32, NMX_OP_TRISOLVE,
+  NMX_LINALG_END
+};
+#define NMX_CHOL_MAX_N 128
 #define NMX_OP_WORDS 8
 
 typedef struct nmx_program {

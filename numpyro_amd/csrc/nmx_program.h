@@ -10,6 +10,13 @@
 // a lane adds its elements i = lane, lane + 64, ... in order, the 64 partial sums are combined by
 // a butterfly (every lane ends with the same bits); a cumsum is a wave scan per chunk of 64 with
 // the carry of the chunk before.  No atomics.
+//
+// The dense ops (cholesky, trisolve; n <= NMX_CHOL_MAX_N = 128, so a lane holds at most two rows)
+// work by matrix row: row i belongs to lane i % 64, which is not the owner of the flat element
+// i * n + j.  The cholesky forward therefore ends with a barrier (its factor is written by row
+// owners); every other final write of the four bodies is made by the element's owner lane: the
+// solution of a trisolve by lane i % 64, the operands' adjoints in a last pass over the flat
+// elements, after a barrier.  n comes from the op word, so all 64 lanes reach every barrier.
 #pragma once
 #include <math.h>
 
@@ -169,6 +176,10 @@ struct NmxProgram {
           v[o.dst + i] = logf(s) + m;
         }
       }
+    } else if (__builtin_expect(o.op == NMX_OP_CHOLESKY, 0)) {
+      cholesky_forward(o, v, lane);
+    } else if (__builtin_expect(o.op == NMX_OP_TRISOLVE, 0)) {
+      trisolve_forward(o, v, lane);
     } else {  // NMX_OP_CONCAT
       for (int i = lane; i < o.n; i += 64) v[o.dst + i] = i < o.aux ? operand(v, o.a, i) : operand(v, o.b, i - o.aux);
     }
@@ -258,11 +269,143 @@ struct NmxProgram {
         const float w = d == -INFINITY ? 0.0f : expf(v[o.a + e] - d);
         g[o.a + e] += g[o.dst + i] * w;
       }
+    } else if (__builtin_expect(o.op == NMX_OP_CHOLESKY, 0)) {
+      cholesky_reverse(o, v, g, lane);
+    } else if (__builtin_expect(o.op == NMX_OP_TRISOLVE, 0)) {
+      trisolve_reverse(o, v, g, lane);
     } else {  // NMX_OP_CONCAT: each part by the owner of the operand's element
       if (o.a >= 0)
         for (int i = lane; i < o.aux; i += 64) g[o.a + i] += g[o.dst + i];
       if (o.b >= 0)
         for (int j = lane; j < o.n - o.aux; j += 64) g[o.b + j] += g[o.dst + o.aux + j];
+    }
+  }
+
+  // ---- the dense ops: row i of a matrix is worked on by lane i % 64, rows `lane` and `lane + 64`
+  // (n <= NMX_CHOL_MAX_N = 128).  No loop depends on a value: bad input gives NaN and returns.
+  //
+  // L = chol(A) column by column, left-looking: column j needs row j's earlier columns (written by
+  // lane j % 64, hence the barrier) and the lane's own rows; the pivot travels by a shuffle.
+  __device__ __forceinline__ void cholesky_forward(const NmxOp& o, float* v, int lane) const {
+    const int n = o.aux;
+    NMX_DCHECK(n >= 1 && n <= NMX_CHOL_MAX_N && o.n == n * n && o.a >= 0 && o.a + o.n <= o.dst);
+    const float* A = v + o.a;
+    float* L = v + o.dst;
+    for (int e = lane; e < o.n; e += 64) {  // the strict upper triangle, by the owner of each element
+      const int i = e / n;
+      if (e - i * n > i) L[e] = 0.0f;
+    }
+    const int i0 = lane, i1 = lane + 64;
+    for (int j = 0; j < n; ++j) {
+      __syncthreads();
+      const float* Lj = L + j * n;
+      float s0 = 0.0f, s1 = 0.0f;
+      if (i0 >= j && i0 < n) {
+        float s = 0.0f;
+        for (int k = 0; k < j; ++k) s += L[i0 * n + k] * Lj[k];
+        s0 = A[i0 * n + j] - s;
+      }
+      if (i1 >= j && i1 < n) {
+        float s = 0.0f;
+        for (int k = 0; k < j; ++k) s += L[i1 * n + k] * Lj[k];
+        s1 = A[i1 * n + j] - s;
+      }
+      const float pivot = __shfl(j < 64 ? s0 : s1, j & 63, 64);
+      const float d = (pivot > 0.0f && pivot < INFINITY) ? sqrtf(pivot) : NAN;
+      if (i0 >= j && i0 < n) L[i0 * n + j] = i0 == j ? d : s0 / d;
+      if (i1 >= j && i1 < n) L[i1 * n + j] = i1 == j ? d : s1 / d;
+    }
+    __syncthreads();  // the factor was written by row owners: later ops read it by flat element
+  }
+
+  // Murray (2016), "Differentiation of the Cholesky decomposition", the unblocked level-2 reverse
+  // sweep, in place on the lower triangle of Lbar (the adjoint slots of dst, dead after this op).
+  // Column j of Lbar is final once step j has run and is never written afterwards, so its scaling
+  // by 1 / L[j][j] waits for the last pass, where the owner of each flat element (r, c) of A adds
+  // half of the (max, min) entry: g_a += (P + P^T) / 2 without a write to another lane's element.
+  __device__ __forceinline__ void cholesky_reverse(const NmxOp& o, const float* v, float* g, int lane) const {
+    const int n = o.aux;
+    const float* L = v + o.dst;
+    float* Lb = g + o.dst;
+    for (int j = n - 1; j >= 0; --j) {
+      __syncthreads();
+      const float* Lj = L + j * n;
+      float* Lbj = Lb + j * n;
+      const float d = Lj[j];
+      float t = 0.0f;
+      for (int i = lane; i < n; i += 64)
+        if (i > j) t += L[i * n + j] * Lb[i * n + j];
+      t = nmx_wave_sum(t);
+      const float db = (Lbj[j] - t / d) / d;
+      for (int k = lane; k < j; k += 64) {  // row j, by column
+        float s = 0.0f;
+        for (int i = j + 1; i < n; ++i) s += Lb[i * n + j] * L[i * n + k];
+        Lbj[k] -= db * Lj[k] + s / d;
+      }
+      for (int i = lane; i < n; i += 64) {  // the rows below, by row
+        if (i <= j) continue;
+        const float cb = Lb[i * n + j] / d;
+        for (int k = 0; k < j; ++k) Lb[i * n + k] -= cb * Lj[k];
+      }
+      __syncthreads();  // every lane has read the diagonal's adjoint
+      if (lane == (j & 63)) Lbj[j] = db;
+    }
+    __syncthreads();
+    for (int e = lane; e < o.n; e += 64) {
+      const int r = e / n, c = e - r * n;
+      const int i = r > c ? r : c, j = r > c ? c : r;
+      const float m = i > j ? Lb[i * n + j] / L[j * n + j] : Lb[e];
+      g[o.a + e] += 0.5f * m;
+    }
+  }
+
+  // x = L^-1 b by columns: once x[k] is known (a shuffle from its row's lane) every later row
+  // subtracts L[i][k] x[k]; an element's updates run in column order and stay in its lane's registers
+  __device__ __forceinline__ void trisolve_forward(const NmxOp& o, float* v, int lane) const {
+    const int n = o.n;
+    NMX_DCHECK(n >= 1 && n <= NMX_CHOL_MAX_N);
+    const float* L = o.a >= 0 ? v + o.a : p.consts + ~o.a;
+    const int i0 = lane, i1 = lane + 64;
+    float y0 = i0 < n ? operand(v, o.b, i0) : 0.0f;
+    float y1 = i1 < n ? operand(v, o.b, i1) : 0.0f;
+    for (int k = 0; k < n; ++k) {
+      const float xk = __shfl(k < 64 ? y0 : y1, k & 63, 64) / L[k * n + k];
+      if (i0 == k) y0 = xk;
+      else if (i0 > k && i0 < n) y0 -= L[i0 * n + k] * xk;
+      if (i1 == k) y1 = xk;
+      else if (i1 > k && i1 < n) y1 -= L[i1 * n + k] * xk;
+    }
+    if (i0 < n) v[o.dst + i0] = y0;
+    if (i1 < n) v[o.dst + i1] = y1;
+  }
+
+  // w = L^-T g_dst by back substitution, columns from the last; g_b += w; then, w stored in dst's
+  // adjoint slots (dead after this op), g_L[i][j] -= w[i] x[j] by the owner of each flat element
+  __device__ __forceinline__ void trisolve_reverse(const NmxOp& o, const float* v, float* g, int lane) const {
+    const int n = o.n;
+    const float* L = o.a >= 0 ? v + o.a : p.consts + ~o.a;
+    const int i0 = lane, i1 = lane + 64;
+    float y0 = i0 < n ? g[o.dst + i0] : 0.0f;
+    float y1 = i1 < n ? g[o.dst + i1] : 0.0f;
+    for (int k = n - 1; k >= 0; --k) {
+      const float wk = __shfl(k < 64 ? y0 : y1, k & 63, 64) / L[k * n + k];
+      if (i0 == k) y0 = wk;
+      else if (i0 < k) y0 -= L[k * n + i0] * wk;
+      if (i1 == k) y1 = wk;
+      else if (i1 < k) y1 -= L[k * n + i1] * wk;
+    }
+    if (o.b >= 0) {
+      if (i0 < n) g[o.b + i0] += y0;
+      if (i1 < n) g[o.b + i1] += y1;
+    }
+    if (o.a >= 0) {
+      if (i0 < n) g[o.dst + i0] = y0;
+      if (i1 < n) g[o.dst + i1] = y1;
+      __syncthreads();
+      for (int e = lane; e < n * n; e += 64) {
+        const int i = e / n, j = e - i * n;
+        if (j <= i) g[o.a + e] -= g[o.dst + i] * v[o.dst + j];
+      }
     }
   }
 
@@ -273,7 +416,8 @@ struct NmxProgram {
   }
   // z slots are referenced at any offset: their adjoints have no fixed lane
   __device__ __forceinline__ bool touches_z(const NmxOp& o) const {
-    const bool b_is_operand = (o.op >= NMX_OP_ADD && o.op < NMX_OP_REDUCE_SUM) || o.op == NMX_OP_CONCAT;
+    const bool b_is_operand =
+        (o.op >= NMX_OP_ADD && o.op < NMX_OP_REDUCE_SUM) || o.op == NMX_OP_CONCAT || o.op == NMX_OP_TRISOLVE;
     return (o.a >= 0 && o.a < p.dim) || (b_is_operand && o.b >= 0 && o.b < p.dim);
   }
 

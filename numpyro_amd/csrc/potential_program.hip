@@ -22,6 +22,7 @@ __global__ __launch_bounds__(64) void k_program(NmxProgram prog, nmx_eval_batch 
 const char* const OP_NAMES[NMX_NUM_OPCODES] = {"neg", "exp", "log", "sqrt", "tanh", "log1p", "square", "softplus",
                                                "lgamma", "add", "sub", "mul", "div", "pow", "reduce_sum",
                                                "gather", "matvec", "cumsum", "logsumexp", "concat"};
+const char* const LINALG_NAMES[NMX_LINALG_END - NMX_OP_CHOLESKY] = {"cholesky", "trisolve"};
 const char* const DRAW_NAMES[NMX_DRAW_END - NMX_DRAW_NORMAL] = {"draw_normal", "draw_exponential", "draw_cauchy",
                                                                 "draw_gamma", "draw_bernoulli", "draw_poisson",
                                                                 "draw_uniform", "draw_binomial"};
@@ -46,8 +47,10 @@ int nmx_program_check_impl(const nmx_program* hp, bool predictive, const int32_t
     const int32_t* w = p.ops + (size_t)k * NMX_OP_WORDS;
     const int op = w[0], dst = w[1], a = w[2], b = w[3], n = w[4], sa = w[5], sb = w[6], aux = w[7];
     const bool draw = predictive && op >= NMX_DRAW_NORMAL && op < NMX_DRAW_END;
-    if (!draw && (op < 0 || op >= NMX_NUM_OPCODES)) return nmx_fail(NMX_ERR_INVALID, "op %d: bad opcode %d", k, op);
-    const char* nm = draw ? DRAW_NAMES[op - NMX_DRAW_NORMAL] : OP_NAMES[op];
+    const bool linalg = op >= NMX_OP_CHOLESKY && op < NMX_LINALG_END;
+    if (!draw && !linalg && (op < 0 || op >= NMX_NUM_OPCODES))
+      return nmx_fail(NMX_ERR_INVALID, "op %d: bad opcode %d", k, op);
+    const char* nm = draw ? DRAW_NAMES[op - NMX_DRAW_NORMAL] : linalg ? LINALG_NAMES[op - NMX_OP_CHOLESKY] : OP_NAMES[op];
     if (n <= 0) return nmx_fail(NMX_ERR_INVALID, "op %d (%s): count %d <= 0", k, nm, n);
     const int64_t dst_len = op == NMX_OP_REDUCE_SUM ? 1 : n;
     if (dst != cursor || cursor + dst_len > p.num_slots)
@@ -81,6 +84,30 @@ int nmx_program_check_impl(const nmx_program* hp, bool predictive, const int32_t
           return nmx_fail(NMX_ERR_INVALID, "op %d (%s): second parameter %s %d (x%lld) out of range", k, nm,
                           b >= 0 ? "slot" : "constant", b >= 0 ? b : ~b, (long long)lb);
       }
+    } else if (op == NMX_OP_CHOLESKY) {
+      if (aux < 1 || aux > NMX_CHOL_MAX_N)
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): matrix dimension %d (aux) outside [1, %d]", k, nm, aux,
+                        NMX_CHOL_MAX_N);
+      if (n != aux * aux)
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): count %d is not %d x %d", k, nm, n, aux, aux);
+      if (!slot_ok(a, n))
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): matrix operand slot %d of %d x %d elements out of range", k, nm, a,
+                        aux, aux);
+    } else if (op == NMX_OP_TRISOLVE) {
+      if (n > NMX_CHOL_MAX_N)
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): dimension %d above %d", k, nm, n, NMX_CHOL_MAX_N);
+      const int64_t la = (int64_t)n * n, lb = n;
+      if (a >= 0 ? !slot_ok(a, la) : !const_ok(a, la))
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): matrix operand %s %d of %d x %d elements out of range", k, nm,
+                        a >= 0 ? "slot" : "constant", a >= 0 ? a : ~a, n, n);
+      if (b >= 0 ? !slot_ok(b, lb) : !const_ok(b, lb))
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): right-hand side %s %d (x%d) out of range", k, nm,
+                        b >= 0 ? "slot" : "constant", b >= 0 ? b : ~b, n);
+      if (a < 0 && b < 0) return nmx_fail(NMX_ERR_INVALID, "op %d (%s): both operands constant", k, nm);
+      // as for the elementwise ops: no barrier between the two updates of the reverse op
+      if (!predictive && a >= 0 && b >= 0 && a < p.dim && b < p.dim && a < b + lb && b < a + la)
+        return nmx_fail(NMX_ERR_INVALID, "op %d (%s): operands z[%d:%lld] and z[%d:%lld] overlap", k, nm, a,
+                        (long long)(a + la), b, (long long)(b + lb));
     } else if (op < NMX_OP_REDUCE_SUM) {
       const bool binary = op >= NMX_OP_ADD;
       if ((sa != 0 && sa != 1) || (sb != 0 && sb != 1))

@@ -11,14 +11,15 @@ Normal (continuous.py:2171), HalfCauchy (:700), Exponential (:455), Gamma (:490)
 (discrete.py:748; observed sites only), Uniform (continuous.py:2431), Beta (:165), Pareto (:2230),
 BinomialProbs / BinomialLogits / Binomial (discrete.py:172, :243, :298; observed sites only),
 Dirichlet (continuous.py), CategoricalProbs / CategoricalLogits / Categorical (discrete.py) and
-MixtureSameFamily (mixtures.py), the last two kinds as observed sites only;
+MixtureSameFamily (mixtures.py), the last two kinds as observed sites only; MultivariateNormal keeps a
+symbolic covariance_matrix or scale_tril for the program compiler;
 ``.to_event`` / ``.expand`` (distribution.py:377-420).
 """
 from __future__ import annotations
 
 import numpy as np
 
-from .jnp import shape_of
+from .jnp import Sym, shape_of
 
 
 def _bshape(*params):
@@ -351,18 +352,27 @@ class GaussianRandomWalk(Distribution):
 
 
 class MultivariateNormal(Distribution):
+    """numpyro/distributions/continuous.py MultivariateNormal.  A constant ``scale_tril`` is kept as
+    the covariance it stands for; a symbolic ``covariance_matrix`` or ``scale_tril`` (an expression
+    of latent sites) is kept as it is, for the program compiler (``matrix_shape`` is its full
+    shape: batch dimensions are the compiler's to refuse)."""
+
     def __init__(self, loc=0.0, covariance_matrix=None, precision_matrix=None, scale_tril=None):
-        if scale_tril is not None:
+        self.scale_tril = None
+        if scale_tril is not None and isinstance(scale_tril, Sym):
+            self.scale_tril = scale_tril
+        elif scale_tril is not None:
             st = np.asarray(scale_tril, np.float64)
-            covariance_matrix = st @ st.T
-        mats = [m for m in (covariance_matrix, precision_matrix) if m is not None]
+            covariance_matrix = st @ np.swapaxes(st, -1, -2)
+        mats = [m for m in (covariance_matrix, precision_matrix, self.scale_tril) if m is not None]
         if len(mats) != 1:
             raise ValueError("One of `covariance_matrix`, `precision_matrix`, `scale_tril` must be specified.")
-        d = shape_of(mats[0])[-1]
+        self.matrix_shape = tuple(shape_of(mats[0]))
+        d = self.matrix_shape[-1]
         super().__init__((), (d,))
         self.loc = loc
         self.covariance_matrix, self.precision_matrix = covariance_matrix, precision_matrix
 
     def params(self):
         return {"loc": self.loc, "covariance_matrix": self.covariance_matrix,
-                "precision_matrix": self.precision_matrix}
+                "precision_matrix": self.precision_matrix, "scale_tril": self.scale_tril}

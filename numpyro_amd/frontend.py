@@ -16,7 +16,8 @@ the model to the program compiler (numpyro_amd/program.py compile_model), which 
 traced log-joint to a straight-line program of primitive operations evaluated, with its
 reverse-mode adjoint, by one HIP kernel (csrc/potential_program.hip).  A model that matches a
 fused kernel always gets it; a model outside the program compiler's class (rank-2 latents,
-batched simplex sites, reparam configs, operations outside numpyro_amd.jnp) is refused by both.
+batched simplex or MultivariateNormal sites, reparam configs, operations outside numpyro_amd.jnp)
+is refused by both.
 """
 from __future__ import annotations
 

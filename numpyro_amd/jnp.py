@@ -1,7 +1,8 @@
 """The array functions the reference's example models call on jax.numpy (matmul, dot, tanh,
-exp, log, log1p, sqrt, square, expit, sum, cumsum, logsumexp (jax.scipy.special's), concatenate,
-zeros, ones, shape; indexing a vector), working on NumPy / torch arrays and on the symbolic values of
-latent sites while the model front end traces a model (numpyro_amd/frontend.py).  Write
+exp, log, log1p, sqrt, square, power, expit, sum, cumsum, logsumexp (jax.scipy.special's),
+concatenate, zeros, ones, eye, shape, linalg.cholesky; indexing a vector), working on NumPy / torch
+arrays and on the symbolic values of latent sites (of rank <= 2 in elementwise expressions) while
+the model front end traces a model (numpyro_amd/frontend.py).  Write
 ``from numpyro_amd import jnp`` where a numpyro model has ``import jax.numpy as jnp``."""
 from __future__ import annotations
 
@@ -158,6 +159,32 @@ def matmul(a, b):
 
 
 dot = matmul
+
+
+def power(x, y):
+    """jax.numpy.power: elementwise x ** y (the program's pow op)."""
+    if isinstance(x, Sym) or isinstance(y, Sym):
+        return Sym("pow", (x, y), np.broadcast_shapes(shape_of(x), shape_of(y)))
+    return np.power(_np(x), _np(y))
+
+
+def eye(n, dtype=None):
+    """float64: a constant times the identity folds on the host unrounded, as every other constant."""
+    return np.eye(n)
+
+
+class linalg:
+    """jax.numpy.linalg: ``cholesky``."""
+
+    @staticmethod
+    def cholesky(a):
+        """The lower Cholesky factor of one square matrix (its lower triangle is read)."""
+        if isinstance(a, Sym):
+            if len(a.shape) != 2 or a.shape[0] != a.shape[1]:
+                raise NotImplementedError(f"linalg.cholesky of a symbolic value of shape {a.shape}: one square "
+                                          "matrix is supported")
+            return Sym("cholesky", (a,), a.shape)
+        return np.linalg.cholesky(_np(a))
 
 
 def zeros(shape, dtype=None):

@@ -26,8 +26,8 @@ from . import distributions as dist
 from . import native
 from .frontend import _base, _host, trace_model
 from .predictive_program import _lgamma
-from .program import (_BINARY, _BINOMIAL, _ELEMENTWISE, _HOST_FWD, _LOGPROB, _SCAN, _UNARY, Program, _Builder,
-                      _Lowering, _Refuse, _ew_mixture, _host_scan_fwd, _refuse, _V)
+from .program import (_BINARY, _BINOMIAL, _ELEMENTWISE, _HOST_FWD, _LINALG, _LOGPROB, _SCAN, _UNARY, Program, _Builder,
+                      _Lowering, _Refuse, _ew_mixture, _host_linalg_fwd, _host_scan_fwd, _lp_mvn, _refuse, _V)
 
 
 class LogLikOutput:
@@ -74,7 +74,7 @@ class LogLikProgram(Program):
         return st, (lib.nmx_last_error().decode(errors="replace") if st else "")
 
     def op_names(self):
-        return [native.OPCODES[o] for o in self.ops[:, 0].tolist()]
+        return [native.op_name(o) for o in self.ops[:, 0].tolist()]
 
     def describe(self):
         return [f"{k}: {nm} dst={o[1]} a={o[2]} b={o[3]} n={o[4]} sa={o[5]} sb={o[6]} aux={o[7]}"
@@ -120,6 +120,8 @@ class LogLikProgram(Program):
                 elif nm == "matvec":
                     M = cp[~b:~b + n * aux].reshape(n, aux)
                     v[:, dst:dst + n] = v[:, a:a + aux] @ M.T
+                elif nm in _LINALG:
+                    _host_linalg_fwd(nm, v, cp, dst, a, b, n, aux)
                 else:
                     assert nm in _SCAN, nm
                     _host_scan_fwd(nm, v, cp, dst, a, b, n, aux)
@@ -186,7 +188,7 @@ def compile_log_likelihood(model, args=(), kwargs=None, given=()):
         shape = _batch_shape(s, base, xv.shape)
         n_site = int(np.prod(shape, dtype=np.int64))
         try:
-            d = {p: lower(getattr(base, p), s.name) for p in pnames}
+            d = {p: lower.vector(getattr(base, p), s.name) for p in pnames}
             if isinstance(base, _BINOMIAL) and not d["total_count"].is_const:
                 _refuse(s.name, "a total_count that depends on a latent site: it must be data")
             x = B.const(xv)
@@ -194,6 +196,8 @@ def compile_log_likelihood(model, args=(), kwargs=None, given=()):
                 logx = B.const(np.log(x.c)) if base.support in ("positive", "simplex") else None
             if isinstance(base, dist.MixtureSameFamily):
                 terms = _ew_mixture(B, lower, base, np.asarray(x.c, np.float64).reshape(-1), s.name)
+            elif isinstance(base, dist.MultivariateNormal):  # one observation per sample, as a Dirichlet vector
+                terms = _lp_mvn(B, lower, base, x, s)
             else:
                 terms = _ELEMENTWISE.get(type(base), expand)(B, d, x, logx)
             # the constant terms are part of the answer: summed on the host, then added once (a scalar

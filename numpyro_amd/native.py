@@ -106,11 +106,22 @@ class EvalBatch(ctypes.Structure):
                 ("num_chains", ctypes.c_int32), ("ldc", ctypes.c_int32)]
 
 
-# enum nmx_opcode (order matters): unary, binary, then the ops that read across elements
+# enum nmx_opcode (order matters): unary, binary, then the ops that read across elements.  cholesky and
+# trisolve are not in this list: LINALG_OPCODES below; OPCODE holds every name, op_name(code) names every code
 OPCODES = ["neg", "exp", "log", "sqrt", "tanh", "log1p", "square", "softplus", "lgamma",
            "add", "sub", "mul", "div", "pow", "reduce_sum", "gather", "matvec", "cumsum", "logsumexp", "concat"]
 OPCODE = {n: i for i, n in enumerate(OPCODES)}
 OP_WORDS = 8  # NMX_OP_WORDS: opcode, dst, a, b, n, sa, sb, aux
+# enum nmx_linalg_opcode: the dense ops, arithmetic ops numbered apart (after concat, before the draws)
+LINALG_BASE = 32
+LINALG_OPCODES = ["cholesky", "trisolve"]
+OPCODE.update({n: LINALG_BASE + i for i, n in enumerate(LINALG_OPCODES)})
+CHOL_MAX_N = 128  # NMX_CHOL_MAX_N
+
+
+def op_name(op):
+    """Name of an arithmetic opcode (nmx_opcode or nmx_linalg_opcode)."""
+    return LINALG_OPCODES[op - LINALG_BASE] if op >= LINALG_BASE else OPCODES[op]
 
 
 # enum nmx_draw_opcode: the draw ops of a predictive program, apart from the arithmetic opcodes

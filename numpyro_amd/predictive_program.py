@@ -30,8 +30,8 @@ from . import distributions as dist
 from . import native
 from .frontend import _base, _host, trace_model
 from .jnp import Sym, shape_of
-from .program import (_BINARY, _HOST_FWD, _LOGPROB, _SCAN, _UNARY, Program, _Builder, _Lowering, _Refuse,
-                      _host_scan_fwd, _refuse, _V)
+from .program import (_BINARY, _HOST_FWD, _LINALG, _LOGPROB, _SCAN, _UNARY, Program, _Builder, _Lowering, _Refuse,
+                      _host_linalg_fwd, _host_scan_fwd, _refuse, _V)
 
 _DRAW_NAME = {v: k for k, v in native.DRAW_OPCODE.items()}
 _U24 = 5.9604644775390625e-08  # 2^-24
@@ -144,7 +144,7 @@ _DRAW = {
 }
 # drawing one of these needs an index that depends on a draw (the category, the component): the
 # program has no such op, so they are supported with data only
-_UNDRAWABLE = (dist.CategoricalProbs, dist.CategoricalLogits, dist.MixtureSameFamily)
+_UNDRAWABLE = (dist.CategoricalProbs, dist.CategoricalLogits, dist.MixtureSameFamily, dist.MultivariateNormal)
 assert set(_DRAW) | set(_UNDRAWABLE) == set(_LOGPROB) and not set(_DRAW) & set(_UNDRAWABLE)
 _INTEGER = (dist.BernoulliLogits, dist.BernoulliProbs, dist.Poisson, dist.BinomialProbs, dist.BinomialLogits,
             dist.CategoricalProbs, dist.CategoricalLogits)
@@ -204,7 +204,7 @@ class PredictiveProgram(Program):
         return st, (lib.nmx_last_error().decode(errors="replace") if st else "")
 
     def op_names(self):
-        return [_DRAW_NAME[o] if o >= native.DRAW_BASE else native.OPCODES[o] for o in self.ops[:, 0].tolist()]
+        return [_DRAW_NAME[o] if o >= native.DRAW_BASE else native.op_name(o) for o in self.ops[:, 0].tolist()]
 
     def describe(self):
         return [f"{k}: {nm} dst={o[1]} a={o[2]} b={o[3]} n={o[4]} sa={o[5]} sb={o[6]} aux={o[7]}"
@@ -264,6 +264,8 @@ class PredictiveProgram(Program):
                     v[:, dst:dst + n] = v[:, a:a + aux] @ M.T
                 elif nm in _SCAN:
                     _host_scan_fwd(nm, v, cp, dst, a, b, n, aux)
+                elif nm in _LINALG:
+                    _host_linalg_fwd(nm, v, cp, dst, a, b, n, aux)
                 else:
                     par = None if nm in _NO_PARAM else np.broadcast_to(operand(a, n, sa), (S, n))
                     if nm == "draw_binomial":
@@ -526,6 +528,10 @@ def compile_predictive(model, args=(), kwargs=None, given=()):
         if type(base) not in _LOGPROB:
             _refuse(s.name, f"{type(base).__name__} is not supported")
         if type(base) in _UNDRAWABLE and s.obs is None and s.name not in given:
+            if isinstance(base, dist.MultivariateNormal):
+                _refuse(s.name, "drawing a MultivariateNormal site is not supported (predictive programs have no "
+                                "product of a factor with a drawn vector): pass its data, or leave the site out of "
+                                "the model")
             _refuse(s.name, f"drawing a {type(base).__name__} site needs a data-dependent index, which predictive "
                             "programs do not have: pass its data, or leave the site out of the model")
         if len(s.shape) > 1:
@@ -555,7 +561,7 @@ def compile_predictive(model, args=(), kwargs=None, given=()):
             _refuse(s.name, f"a drawn site of {n} elements (more than 2^24, the draw counter's element field)")
         first = B.n_draws
         try:
-            d = {p: lower(getattr(base, p), s.name) for p in _LOGPROB[type(base)][1]}
+            d = {p: lower.vector(getattr(base, p), s.name) for p in _LOGPROB[type(base)][1]}
             for p, val in d.items():
                 if val.n not in (1, n):
                     _refuse(s.name, f"parameter {p!r} of {val.n} elements at a site of {n}")

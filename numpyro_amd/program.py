@@ -26,8 +26,16 @@ vector per site (``simplex``: K - 1 unconstrained coordinates, stick breaking bu
 from the cumsum and concat ops); observed sites from those plus BernoulliLogits / BernoulliProbs /
 Poisson / BinomialLogits / BinomialProbs (with a total_count that is data), CategoricalProbs /
 CategoricalLogits (a parameter of rank 1) and MixtureSameFamily of a Categorical with univariate
-continuous components (the N x K table through a row-wise logsumexp); parameters that are
-constants or expressions of latents over numpyro_amd.jnp's operations.  Anything else raises
+continuous components (the N x K table through a row-wise logsumexp); MultivariateNormal as an
+observed site (loc constant or symbolic) or as one latent vector (loc constant), its
+covariance_matrix or scale_tril constant or symbolic, n <= 128: -0.5 |L^-1 (x - loc)|^2 -
+sum(log diag L) - n/2 log 2 pi from the cholesky and trisolve ops (include/numpyro_amd.h), a
+constant covariance factorised here and applied through matvec; parameters that are constants or
+expressions of latents over numpyro_amd.jnp's operations.  Values of rank 2 (a kernel matrix built
+from latents) are flat row-major values: elementwise operations between equal shapes and with
+scalars are the ops unchanged, any other NumPy-broadcastable pair gathers the smaller operand;
+reductions, indexing and products of rank-2 values, latents of rank 2, rank > 2, a symbolic
+precision_matrix, and batched or plated MultivariateNormal sites are refused.  Anything else raises
 NotImplementedError naming the site.
 """
 from __future__ import annotations
@@ -137,6 +145,85 @@ def _host_scan_rev(nm, v, g, dst, a, b, n, aux):
 
 
 _SCAN = ("cumsum", "logsumexp", "concat")
+_LINALG = ("cholesky", "trisolve")
+
+
+def _host_cholesky(A):
+    """Lower Cholesky factors of A [C, n, n] (its lower triangle), column by column as the kernel:
+    L[i][j] = (A[i][j] - sum_{k < j} L[i][k] L[j][k]) / L[j][j]; a pivot that is not positive and
+    finite is NaN, and so is everything computed from it."""
+    n = A.shape[-1]
+    L = np.zeros_like(A)
+    for j in range(n):
+        s = A[:, j:, j] - np.einsum("cik,ck->ci", L[:, j:, :j], L[:, j, :j])
+        piv = s[:, 0]
+        ok = (piv > 0) & np.isfinite(piv)
+        d = np.where(ok, np.sqrt(np.where(ok, piv, 1)), np.nan).astype(A.dtype)
+        L[:, j:, j] = s / d[:, None]
+        L[:, j, j] = d
+    return L
+
+
+def _host_cholesky_rev(L, Lbar):
+    """Adjoint of A from the adjoint of L = chol(A) [C, n, n]: (P + P^T) / 2 with
+    P = L^-T Phi(L^T Lbar) L^-1, by the unblocked reverse sweep of Murray (2016), "Differentiation of
+    the Cholesky decomposition", without its last halving of the diagonal: M = tril(P + P^T)."""
+    n = L.shape[-1]
+    M = np.tril(Lbar).copy()
+    for j in range(n - 1, -1, -1):
+        d = L[:, j, j]
+        cb = M[:, j + 1:, j]
+        db = (M[:, j, j] - (L[:, j + 1:, j] * cb).sum(1) / d) / d
+        cb = cb / d[:, None]
+        M[:, j + 1:, j] = cb
+        M[:, j, :j] -= db[:, None] * L[:, j, :j] + np.einsum("ci,cik->ck", cb, L[:, j + 1:, :j])
+        M[:, j + 1:, :j] -= cb[:, :, None] * L[:, j, None, :j]
+        M[:, j, j] = db
+    return 0.5 * (M + np.swapaxes(np.tril(M, -1), 1, 2))
+
+
+def _host_trisolve(L, b, transpose=False):
+    """L^-1 b (or L^-T b) for L [C or 1, n, n] lower triangular and b [C or 1, n], by columns."""
+    n = L.shape[-1]
+    y = np.broadcast_to(b, (max(L.shape[0], b.shape[0]), n)).copy()
+    for k in (range(n - 1, -1, -1) if transpose else range(n)):
+        y[:, k] = y[:, k] / L[:, k, k]
+        if transpose:
+            y[:, :k] -= L[:, k, :k] * y[:, k:k + 1]
+        else:
+            y[:, k + 1:] -= L[:, k + 1:, k] * y[:, k:k + 1]
+    return y
+
+
+def _host_linalg_operands(v, cp, a, b, n):
+    """(L [C or 1, n, n], rhs [C or 1, n]) of a trisolve."""
+    L = v[:, a:a + n * n] if a >= 0 else cp[None, ~a:~a + n * n]
+    rhs = v[:, b:b + n] if b >= 0 else cp[None, ~b:~b + n]
+    return L.reshape(-1, n, n), rhs
+
+
+def _host_linalg_fwd(nm, v, cp, dst, a, b, n, aux):
+    """Forward of cholesky / trisolve on the value table v [C, S] (any float dtype)."""
+    C = v.shape[0]
+    if nm == "cholesky":
+        v[:, dst:dst + n] = _host_cholesky(v[:, a:a + n].reshape(C, aux, aux)).reshape(C, n)
+    else:
+        v[:, dst:dst + n] = _host_trisolve(*_host_linalg_operands(v, cp, a, b, n))
+
+
+def _host_linalg_rev(nm, v, g, cp, dst, a, b, n, aux):
+    """Reverse of cholesky / trisolve: the operands' adjoints in g [C, S]."""
+    C = v.shape[0]
+    if nm == "cholesky":
+        g[:, a:a + n] += _host_cholesky_rev(v[:, dst:dst + n].reshape(C, aux, aux),
+                                            g[:, dst:dst + n].reshape(C, aux, aux)).reshape(C, n)
+        return
+    L, _ = _host_linalg_operands(v, cp, a, b, n)
+    w = _host_trisolve(L, g[:, dst:dst + n], transpose=True)
+    if b >= 0:
+        g[:, b:b + n] += w
+    if a >= 0:
+        g[:, a:a + n * n] -= np.tril(w[:, :, None] * v[:, None, dst:dst + n]).reshape(C, n * n)
 
 
 class Program:
@@ -185,8 +272,7 @@ class Program:
         return st, (lib.nmx_last_error().decode(errors="replace") if st else "")
 
     def describe(self):
-        names = native.OPCODES
-        return [f"{k}: {names[o[0]]} dst={o[1]} a={o[2]} b={o[3]} n={o[4]} sa={o[5]} sb={o[6]} aux={o[7]}"
+        return [f"{k}: {native.op_name(o[0])} dst={o[1]} a={o[2]} b={o[3]} n={o[4]} sa={o[5]} sb={o[6]} aux={o[7]}"
                 for k, o in enumerate(self.ops.tolist())]
 
     # ------------------------------------------------------------------ float64 interpreter
@@ -198,7 +284,7 @@ class Program:
         C, S, D = Z.shape[0], self.num_slots, self.dim
         assert Z.shape[1] == D
         cp = self.consts.astype(np.float64) if f32_consts else self.consts64
-        ix, names = self.index, native.OPCODES
+        ix = self.index
         v = np.zeros((C, S))
         g = np.zeros((C, S))
         v[:, :D] = Z
@@ -210,7 +296,7 @@ class Program:
         ops = self.ops.tolist()
         with np.errstate(all="ignore"):
             for op, dst, a, b, n, sa, sb, aux in ops:
-                nm = names[op]
+                nm = native.op_name(op)
                 if nm in _UNARY:
                     v[:, dst:dst + n] = _HOST_FWD[nm](operand(a, n, sa))
                 elif nm in _BINARY:
@@ -222,11 +308,13 @@ class Program:
                 elif nm == "matvec":
                     M = cp[~b:~b + n * aux].reshape(n, aux)
                     v[:, dst:dst + n] = v[:, a:a + aux] @ M.T
+                elif nm in _LINALG:
+                    _host_linalg_fwd(nm, v, cp, dst, a, b, n, aux)
                 else:
                     _host_scan_fwd(nm, v, cp, dst, a, b, n, aux)
             g[:, S - 1] = 1.0
             for op, dst, a, b, n, sa, sb, aux in reversed(ops):
-                nm = names[op]
+                nm = native.op_name(op)
                 gd = g[:, dst:dst + (1 if nm == "reduce_sum" else n)]
                 if nm in _UNARY or nm in _BINARY:
                     x = operand(a, n, sa)
@@ -247,6 +335,8 @@ class Program:
                 elif nm == "matvec":
                     M = cp[~b:~b + n * aux].reshape(n, aux)
                     g[:, a:a + aux] += gd @ M
+                elif nm in _LINALG:
+                    _host_linalg_rev(nm, v, g, cp, dst, a, b, n, aux)
                 else:
                     _host_scan_rev(nm, v, g, dst, a, b, n, aux)
         return v[:, S - 1].copy(), g[:, :D].copy()
@@ -256,9 +346,13 @@ class Program:
         """Arithmetic operations of one evaluation, forward + reverse (a transcendental counts 1)."""
         f = 0.0
         for op, dst, a, b, n, sa, sb, aux in self.ops.tolist():
-            nm = native.OPCODES[op]
+            nm = native.op_name(op)
             if nm == "logsumexp":  # per element: max, subtract, exp, add; and subtract, exp, multiply, add
                 f += 8.0 * n * aux
+            elif nm == "cholesky":  # aux^3 / 3 forward, twice that in the reverse sweep
+                f += float(aux) ** 3
+            elif nm == "trisolve":  # n^2 forward, n^2 back substitution, n^2 for the factor's adjoint
+                f += 3.0 * n * n
             elif nm == "concat":  # moves only
                 continue
             else:
@@ -272,12 +366,14 @@ class Program:
         Constants and indices are shared by all chains and stay cached."""
         el = self.num_slots + 2 * self.dim  # zero fill, z in, grad out
         for op, dst, a, b, n, sa, sb, aux in self.ops.tolist():
-            nm = native.OPCODES[op]
+            nm = native.op_name(op)
             if nm == "matvec":
                 src = [aux]
+            elif nm == "trisolve":
+                src = [ln for r, ln in ((a, n * n), (b, n)) if r >= 0]
             elif nm == "gather":
                 src = [n]
-            elif nm in ("reduce_sum", "cumsum"):
+            elif nm in ("reduce_sum", "cumsum", "cholesky"):
                 src = [n]
             elif nm == "logsumexp":
                 src = [n * aux]
@@ -457,6 +553,25 @@ class _Builder:
         ra, rb, n = self._ref(a), self._ref(b), a.n + b.n
         return self._emit("concat", n, ra, rb, n, 1, 1, a.n, ("concat", ra, rb, a.n, b.n))
 
+    def cholesky(self, a, m):
+        """The lower Cholesky factor of the flat row-major m x m value a: m * m elements."""
+        a = self.const(a)
+        assert a.n == m * m, (a.n, m)
+        if a.is_const:
+            return self.const(_const_cholesky(a.c.reshape(m, m)).reshape(-1))
+        return self._emit("cholesky", m * m, a.slot, 0, m * m, 1, 0, m, ("cholesky", a.slot, m))
+
+    def trisolve(self, L, b):
+        """L^-1 b for the flat row-major n x n lower-triangular L and b of n elements."""
+        L, b = self.const(L), self.const(b)
+        n = b.n
+        assert L.n == n * n, (L.n, n)
+        if L.is_const and b.is_const:
+            with np.errstate(all="ignore"):
+                return self.const(_host_trisolve(L.c.reshape(1, n, n), b.c[None])[0])
+        ra, rb = self._ref(L), self._ref(b)
+        return self._emit("trisolve", n, ra, rb, n, 1, 1, 0, ("trisolve", ra, rb, n))
+
     def unary(self, name):
         return lambda x: self.ew(name, x)
 
@@ -495,7 +610,7 @@ class _Builder:
                 if o[0] == draws["draw_binomial"]:
                     return (2, 3)
                 return (2,) if o[0] >= draws["draw_gamma"] and o[0] != draws["draw_uniform"] else ()
-            return (2, 3) if o[0] in binary or o[0] == OPCODE["concat"] else (2,)
+            return (2, 3) if o[0] in binary or o[0] in (OPCODE["concat"], OPCODE["trisolve"]) else (2,)
 
         def slot_refs(o):
             return [o[f] for f in fields(o) if o[f] >= dim]
@@ -661,6 +776,63 @@ def _lp_categorical_logits(B, d, x, logx):
 _CATEGORICAL = (dist.CategoricalProbs, dist.CategoricalLogits)
 
 
+def _const_cholesky(A):
+    """float64 factor of a constant covariance; one that is not positive definite is refused."""
+    try:
+        return np.linalg.cholesky(0.5 * (A + A.T))
+    except np.linalg.LinAlgError:
+        raise NotImplementedError("a constant matrix that is not positive definite") from None
+
+
+def _lp_mvn(B, lower, base, x, site):
+    """MultivariateNormal at the vector x [n]: -0.5 |L^-1 (x - loc)|^2 - sum log diag L - n/2 log 2 pi.
+    A symbolic covariance goes through the cholesky op and a symbolic factor through trisolve; a
+    constant one is factorised here in float64, its L^-1 applied by matvec and its log-determinant
+    folded, so that a model with constant covariances alone emits neither op."""
+    n, ms = int(base.event_shape[0]), tuple(base.matrix_shape)
+    if len(ms) != 2 or ms[0] != ms[1]:
+        _refuse(site.name, f"a MultivariateNormal with a matrix of shape {ms}: batch dimensions are not supported "
+                           "(one n x n matrix is)")
+    if site.plates:
+        _refuse(site.name, f"a MultivariateNormal inside plates {list(site.plates)} is not supported")
+    if n > native.CHOL_MAX_N:
+        _refuse(site.name, f"a MultivariateNormal of {n} dimensions: at most {native.CHOL_MAX_N} are supported (one "
+                           "wave factorises the matrix of a chain)")
+    if isinstance(base.precision_matrix, Sym):
+        _refuse(site.name, "a precision_matrix that depends on a latent site (supported: a symbolic "
+                           "covariance_matrix or scale_tril, a constant precision_matrix)")
+    loc_shape = tuple(np.shape(_host(base.loc)) if not isinstance(base.loc, Sym) else base.loc.shape)
+    if loc_shape not in ((), (1,), (n,)) or x.n != n or tuple(site.shape) != (n,):
+        _refuse(site.name, f"a MultivariateNormal with loc of shape {loc_shape} and a value of {x.n} elements at a "
+                           f"site of shape {tuple(site.shape)}: batch dimensions are not supported (one vector of "
+                           f"{n} is)")
+    if site.obs is None and isinstance(base.loc, Sym):
+        _refuse(site.name, "a latent MultivariateNormal whose loc depends on a latent site (supported: a constant "
+                           "loc with a constant or symbolic covariance_matrix or scale_tril)")
+    diff = x - lower.vector(base.loc, site.name)
+    if base.scale_tril is not None:
+        L = lower(base.scale_tril, site.name)
+    elif isinstance(base.covariance_matrix, Sym):
+        L = B.cholesky(lower(base.covariance_matrix, site.name), n)
+    elif base.covariance_matrix is not None:
+        L = B.const(_const_cholesky(np.asarray(_host(base.covariance_matrix), np.float64)).reshape(-1))
+    else:
+        prec = np.asarray(_host(base.precision_matrix), np.float64)
+        _const_cholesky(prec)  # refuses a precision that is not positive definite
+        L = B.const(_const_cholesky(np.linalg.inv(prec)).reshape(-1))
+    diag = np.arange(n) * (n + 1)
+    if L.is_const:
+        Lc = L.c.reshape(n, n)
+        with np.errstate(all="ignore"):
+            Linv = _host_trisolve(Lc[None], np.eye(n)).T  # row k of the solve is L^-1 e_k
+        w = B.matvec(Linv, diff) if not diff.is_const else B.const(Linv @ diff.c)
+        log_det = B.const(np.log(Lc.reshape(-1)[diag]).sum())
+    else:
+        w = B.trisolve(L, diff)
+        log_det = B.rsum(B.ew("log", B.gather(L, diag)))
+    return [-0.5 * B.rsum(B.ew("square", w)), -log_det, B.const(-n * _HALF_LOG_2PI)]
+
+
 def _lp_mixture(B, lower, base, xv, site):
     """MixtureSameFamily at observations xv [N]: the site's total, the sum of _ew_mixture."""
     return [B.rsum(t) for t in _ew_mixture(B, lower, base, xv, site)]
@@ -676,7 +848,7 @@ def _ew_mixture(B, lower, base, xv, site):
     if entry is None or not entry[2] or isinstance(comp, _VECTOR) or comp.event_shape:
         _refuse(site, f"a mixture of {type(comp).__name__} components (supported: the univariate continuous "
                       "distributions)")
-    w = lower(mixing.probs if isinstance(mixing, dist.CategoricalProbs) else mixing.logits, site)
+    w = lower.vector(mixing.probs if isinstance(mixing, dist.CategoricalProbs) else mixing.logits, site)
     K, N = w.n, xv.size
     if K < 2:
         _refuse(site, "a mixture of fewer than 2 components")
@@ -686,7 +858,7 @@ def _ew_mixture(B, lower, base, xv, site):
     col = np.tile(np.arange(K), N)  # the component of each element of the flat table
     d = {}
     for p in entry[1]:
-        val = lower(getattr(comp, p), site)
+        val = lower.vector(getattr(comp, p), site)
         if val.n not in (1, K):
             _refuse(site, f"component parameter {p!r} of {val.n} elements under {K} mixing weights")
         d[p] = B.gather(val, col) if val.n == K else val  # a scalar keeps stride 0
@@ -721,10 +893,12 @@ _LOGPROB = {
     dist.CategoricalProbs: (_lp_categorical_probs, ("probs",), False),
     dist.CategoricalLogits: (_lp_categorical_logits, ("logits",), False),
     dist.MixtureSameFamily: (None, (), False),  # _lp_mixture lowers the two distributions it holds
+    dist.MultivariateNormal: (None, (), True),  # _lp_mvn lowers loc and the matrix, which is of rank 2
 }
 _BINOMIAL = (dist.BinomialProbs, dist.BinomialLogits)
 # whole-vector distributions: one log density per site, returned as scalar terms
-_VECTOR = (dist.Dirichlet, dist.CategoricalProbs, dist.CategoricalLogits, dist.MixtureSameFamily)
+_VECTOR = (dist.Dirichlet, dist.CategoricalProbs, dist.CategoricalLogits, dist.MixtureSameFamily,
+           dist.MultivariateNormal)
 
 
 # ---- the logit likelihoods elementwise.  x eta - n softplus(eta) is right as a term of a site's
@@ -792,17 +966,27 @@ class _Lowering:
     def __call__(self, x, site):
         if not isinstance(x, Sym):
             a = np.asarray(_host(x), np.float64)
-            if a.ndim > 1:
-                _refuse(site, f"a constant of shape {a.shape} (rank > 1) outside a matmul")
-            return self.B.const(a)
+            if a.ndim > 2:
+                _refuse(site, f"a constant of shape {a.shape} (rank > 2)")
+            return self.B.const(a.reshape(-1))  # rank 2: flat, row-major
         hit = self.seen.get(id(x))
         if hit is not None:
             return hit[1]
-        if len(x.shape) > 1:
-            _refuse(site, f"expression {x!r} of shape {x.shape}: values of rank > 1 are not supported")
+        if len(x.shape) > 2:
+            _refuse(site, f"expression {x!r} of shape {x.shape}: values of rank > 2 are not supported")
         out = self._lower(x, site)
         self.seen[id(x)] = (x, out)
         return out
+
+    def vector(self, x, site):
+        """A value of rank <= 1: a distribution's parameter (the matrix of a MultivariateNormal is
+        lowered by _lp_mvn) or the operand of an operation that takes vectors."""
+        if isinstance(x, Sym):
+            if len(x.shape) > 1:
+                _refuse(site, f"expression {x!r} of shape {x.shape}: values of rank > 1 are not supported")
+        elif np.ndim(_host(x)) > 1:
+            _refuse(site, f"a constant of shape {np.shape(_host(x))} (rank > 1) outside a matmul")
+        return self(x, site)
 
     def _lower(self, x, site):
         B, op = self.B, x.op
@@ -815,16 +999,19 @@ class _Lowering:
         if op == "expit":  # exp(-softplus(-x)): log(expit(x)) then folds to -softplus(-x)
             return B.ew("exp", B.ew("neg", B.ew("softplus", B.ew("neg", self(x.args[0], site)))))
         if op in _BINARY:
-            return B.ew(op, self(x.args[0], site), self(x.args[1], site))
+            return B.ew(op, *(self._broadcast(a, x.shape, site) for a in x.args))
+        if op == "cholesky":
+            return B.cholesky(self(x.args[0], site), x.shape[0])
+        # reductions, joins, indexing and products take vectors: self.vector refuses a value of rank 2
         if op == "sum":
-            return B.rsum(self(x.args[0], site))
+            return B.rsum(self.vector(x.args[0], site))
         if op == "cumsum":
-            return B.cumsum(self(x.args[0], site))
+            return B.cumsum(self.vector(x.args[0], site))
         if op == "logsumexp":
-            v = self(x.args[0], site)
+            v = self.vector(x.args[0], site)
             return B.logsumexp(v, 1, v.n)
         if op == "concatenate":
-            parts = [self(a, site) for a in x.args]
+            parts = [self.vector(a, site) for a in x.args]
             for a, v in zip(x.args, parts):
                 if v.n != int(np.prod(np.shape(_host(a)) if not isinstance(a, Sym) else a.shape, dtype=np.int64)):
                     _refuse(site, "concatenate of a part whose size is not its shape's")
@@ -833,7 +1020,7 @@ class _Lowering:
                 out = B.concat(out, v)
             return out
         if op == "getitem":
-            src, idx = self(x.args[0], site), x.args[1]
+            src, idx = self.vector(x.args[0], site), x.args[1]
             sel = np.arange(src.n)[idx] if isinstance(idx, (int, slice)) else np.asarray(_host(idx))
             if np.ndim(sel) > 1:
                 _refuse(site, "indexing with an index array of rank > 1")
@@ -844,17 +1031,33 @@ class _Lowering:
             if isinstance(a, Sym) == isinstance(b, Sym):
                 _refuse(site, "matmul of two symbolic values (supported: a constant matrix with a symbolic vector)")
             if isinstance(b, Sym):  # M @ v
-                M, vec = np.asarray(_host(a), np.float64), self(b, site)
+                M, vec = np.asarray(_host(a), np.float64), self.vector(b, site)
                 M = M.reshape(1, -1) if M.ndim == 1 else M
             else:  # v @ M
-                M, vec = np.asarray(_host(b), np.float64), self(a, site)
+                M, vec = np.asarray(_host(b), np.float64), self.vector(a, site)
                 M = M.reshape(1, -1) if M.ndim == 1 else M.T
             if M.ndim != 2 or M.shape[1] != vec.n or len(x.shape) > 1:
                 _refuse(site, f"matmul of shapes {np.shape(_host(a)) if not isinstance(a, Sym) else a.shape} and "
                               f"{np.shape(_host(b)) if not isinstance(b, Sym) else b.shape}")
             return B.matvec(M, vec)
         _refuse(site, f"operation {op!r} is not supported (supported: {sorted(_UNARY[:7] + _BINARY)}, expit, sum, "
-                      "cumsum, logsumexp, concatenate, getitem, matmul)")
+                      "cumsum, logsumexp, concatenate, getitem, matmul, linalg.cholesky)")
+
+    def _broadcast(self, a, out_shape, site):
+        """The operand a of an elementwise op of shape out_shape: itself where it has as many elements
+        or one (the ops' stride 0), else broadcast by NumPy's rules: a constant on the host, a symbolic
+        value by a gather with the index np.broadcast_to gives."""
+        size = int(np.prod(out_shape, dtype=np.int64))
+        if not isinstance(a, Sym):
+            c = np.asarray(_host(a), np.float64)
+            if c.size in (1, size) or c.ndim > 2:
+                return self(c.reshape(-1) if c.ndim <= 2 else c, site)
+            return self.B.const(np.broadcast_to(c, out_shape).reshape(-1))
+        v = self(a, site)
+        if v.n in (1, size):
+            return v
+        idx = np.broadcast_to(np.arange(v.n).reshape(a.shape), out_shape).reshape(-1)
+        return self.B.gather(v, idx)
 
 
 def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
@@ -937,7 +1140,7 @@ def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
             _refuse(s.name, f"{type(base).__name__} is not supported")
         expand, pnames, _ = entry
         try:
-            d = {p: lower(getattr(base, p), s.name) for p in pnames}
+            d = {p: lower.vector(getattr(base, p), s.name) for p in pnames}
             if isinstance(base, _BINOMIAL) and not d["total_count"].is_const:
                 _refuse(s.name, "a total_count that depends on a latent site: it must be data")
             if s.obs is None:
@@ -956,6 +1159,8 @@ def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
                 n_site = 1
             if isinstance(base, dist.MixtureSameFamily):
                 terms = _lp_mixture(B, lower, base, np.asarray(x.c, np.float64).reshape(-1), s.name)
+            elif isinstance(base, dist.MultivariateNormal):
+                terms = _lp_mvn(B, lower, base, x, s)
             else:
                 terms = expand(B, d, x, logx)
             if s.obs is None:
