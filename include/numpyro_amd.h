@@ -689,7 +689,9 @@ int nmx_predict_program(const nmx_program* program, const float* samples, int nu
  * are bitwise equal.  Special columns:
  *   p_waic is NaN for S = 1, and NaN in a column that holds a non-finite entry;
  *   lppd is -inf for a column of all -inf, finite if the column has a finite entry and no +inf or
- *   NaN, and NaN if the column holds a NaN.
+ *   NaN, and NaN if the column holds a NaN;
+ *   elpd_loo and pareto_k ("PSIS-LOO" below) are both NaN for a column that holds any non-finite
+ *   entry (NaN, +inf or -inf).
  * ---- */
 #define NMX_POINTWISE_MAX_SPLITS 64
 #define NMX_POINTWISE_MIN_SPLIT_ROWS 16
@@ -712,6 +714,59 @@ int nmx_pointwise_accumulate(const float* table, int num_rows, int64_t ld, int n
                              void* stream);
 /* lppd [num_columns] and p_waic [num_columns] (either may be NULL) of the rows accumulated. */
 int nmx_pointwise_finish(const void* state, int num_columns, float* lppd, float* p_waic, void* stream);
+
+/* ---- PSIS-LOO: Pareto-smoothed importance-sampling leave-one-out cross-validation (Vehtari,
+ *      Gelman and Gabry 2017) of an f32 table [S][ld], per column: elpd_loo, the log predictive
+ *      density of the observation under the posterior that leaves it out, and pareto_k, the shape
+ *      of the generalised Pareto distribution fitted to the largest importance ratios (Zhang and
+ *      Stephens 2009, with the weak prior of the loo package), which says whether elpd_loo of that
+ *      observation can be trusted.
+ *
+ * For a column x_s (s < S) and a tail length M given by the caller (1 <= M < S):
+ *   m = max_s(-x_s) and r_s = (-x_s) - m in f32 with one rounding, so r <= 0: the log importance
+ *   ratios.  Every discrete decision is taken on these f32 values.
+ *   cut = max(the (M+1)-th largest r, NMX_PSIS_LOG_FLT_MIN).  The tail is { r_s > cut } (strict: ties
+ *   at the cutoff stay in the body), T <= M its size, t_0 <= ... <= t_{T-1} its ascending order.
+ *   If T <= 4: pareto_k = +inf and lw_i = t_i (no smoothing).  Otherwise, in f64:
+ *     e_i = exp(t_i) - exp(cut), q = e_{floor(T/4 + 0.5) - 1}, J = 30 + floor(sqrt(T));
+ *     for j = 1..J: b_j = (1 - sqrt(J / (j - 0.5))) / (3 q) + 1 / e_{T-1},
+ *       kappa_j = (sum_i log1p(-b_j e_i)) / T, L_j = T (log(-b_j / kappa_j) - kappa_j - 1);
+ *     w_j = exp(L_j - max L) / sum_j exp(L_j - max L), b = sum_j b_j w_j (a NaN L_j makes b NaN);
+ *     kappa = (sum_i log1p(-b e_i)) / T, sigma = -kappa / b, k = (T kappa + 5) / (T + 10).
+ *     If k or sigma is not finite: lw_i = t_i, and pareto_k = k as it came out.  Otherwise
+ *     p_i = (i + 0.5) / T, g_i = sigma expm1(-k log1p(-p_i)) / k, and for |k| < NMX_PSIS_K_ZERO the
+ *     limit g_i = -sigma log1p(-p_i) (there the two differ by a relative |k log1p(-p_i)| / 2 < 1e-9);
+ *     lw_i = fmin(log(g_i + exp(cut)), 0)  (fmin: a NaN, from a negative sigma, gives 0).
+ *   den = sum_body exp(r_s) + sum_i exp(lw_i), num = (S - T) + sum_i exp(lw_i - t_i) and
+ *   elpd_loo = (log(num) - m) - log(den), rounded to f32 with pareto_k.  A body term's weight times
+ *   its likelihood is exp(r_s + x_s) = exp(-m): the body enters only through den and its count.
+ * The body's exp is the f32 expf; its sum and every step after the sort are f64.  Orders: a thread
+ * of the column's 256 adds the rows tid, tid + 256, ... in order; a sum over the workgroup adds the
+ * 64 lanes of a wave by the xor butterfly (32, 16, ..., 1), then the four waves in order; candidate
+ * j is summed by wave (j - 1) % 4, lane l adding i = l, l + 64, ...  The select's histogram is the
+ * only atomic (integer, in LDS), and the sort erases the order in which the tail was gathered, so
+ * two launches are bitwise equal, and a column's result depends on (S, M) and the column alone, not
+ * on num_columns, ld or the other columns.  Special columns:
+ *   a column that holds a non-finite entry (NaN, +inf or -inf): elpd_loo = pareto_k = NaN;
+ *   a constant column: every r is 0, T = 0, pareto_k = +inf and elpd_loo = the constant (to rounding);
+ *   ratios that span more than e^87: the floor NMX_PSIS_LOG_FLT_MIN is the cutoff, and T < M.
+ * Limits: the tail lives in LDS (12 bytes per entry of the power of two >= M, 96 KiB of the CU's
+ * 160 KiB at NMX_PSIS_MAX_TAIL, which admits S = 2^22 at the default M = ceil(min(S / 5, 3 sqrt(S))));
+ * NMX_PSIS_MAX_ROWS keeps S - T exact in f32 and the row index in an int.
+ * ---- */
+#define NMX_PSIS_MAX_TAIL 8192
+#define NMX_PSIS_MAX_ROWS 16777216 /* 2^24 */
+#define NMX_PSIS_LOG_FLT_MIN -87.33655f
+#define NMX_PSIS_K_ZERO 1e-10
+/* The workspace of nmx_psis_loo: the column-contiguous copy [num_columns][num_rows] of the table. */
+size_t nmx_psis_workspace_bytes(int num_rows, int num_columns);
+/* elpd_loo [num_columns] and pareto_k [num_columns] (either may be NULL, not both) of the first
+ * num_columns columns of table [num_rows][ld] with the tail length `tail`.  Two launches (the
+ * transpose into `workspace`, then one workgroup per column).  NMX_ERR_INVALID, before any launch,
+ * for a NULL table or workspace, num_rows < 2 or > NMX_PSIS_MAX_ROWS, tail < 1, >= num_rows or
+ * > NMX_PSIS_MAX_TAIL, num_columns < 1, ld < num_columns, or both outputs NULL. */
+int nmx_psis_loo(const float* table, int num_rows, int64_t ld, int num_columns, int tail, void* workspace,
+                 float* elpd_loo, float* pareto_k, void* stream);
 
 /* ---- self tests (no reference counterpart; used by tests and smoke()) ---- */
 /* Philox4x32-10 on device: ctr_key is n x {c0,c1,c2,c3,k0,k1}, out is n x 4 words. */

@@ -46,7 +46,8 @@ COMMON_FLAGS = [
 # * no floating-point contraction in the step kernels, the small models' potentials and the
 #   program potential and predictive program (bodies in a header, nmx_program.h, like the small
 #   models; the predictive draws' accept tests round like their NumPy restatement, and so do the
-#   log-likelihood program and the Welford / Chan merges of its pointwise reductions): the
+#   log-likelihood program and the Welford / Chan merges of its pointwise reductions, and the
+#   PSIS kernel's log ratios and sums): the
 #   same device function is inlined into several kernels (the launched step, the persistent
 #   schedule, the sync / async schedules), and whether the backend fuses a * b + c into an FMA
 #   depends on each kernel's code generation -- with contraction off every kernel rounds every
@@ -56,7 +57,8 @@ FILE_FLAGS = {"potential_logreg.hip": ["-fno-slp-vectorize"],
               "potential_small.hip": ["-ffp-contract=off"],
               "potential_program.hip": ["-ffp-contract=off"],
               "predictive_program.hip": ["-ffp-contract=off"],
-              "loglik_program.hip": ["-ffp-contract=off"]}
+              "loglik_program.hip": ["-ffp-contract=off"],
+              "psis.hip": ["-ffp-contract=off"]}
 
 
 def _headers():

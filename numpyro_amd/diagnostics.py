@@ -5,12 +5,14 @@ print_summary tables (:234-342).  Accepts torch tensors as well as arrays."""
 from __future__ import annotations
 
 from collections import OrderedDict
+import math
 from itertools import product
 
 import numpy as np
 
 __all__ = ["autocorrelation", "autocovariance", "effective_sample_size", "gelman_rubin", "hpdi",
-           "split_gelman_rubin", "summary", "print_summary", "print_summary_table", "lppd", "waic"]
+           "split_gelman_rubin", "summary", "print_summary", "print_summary_table", "lppd", "waic",
+           "loo", "pareto_k"]
 
 
 def _np(x):
@@ -200,3 +202,73 @@ def waic(log_lik):
     n = elpd.numel()
     return {"elpd_waic": elpd.sum(), "p_waic": pw.sum(), "lppd": lp.sum(),
             "se": torch.sqrt(n * elpd.var(unbiased=False))}
+
+
+def _rows(table):
+    shape = tuple(table.shape) if hasattr(table, "shape") else np.shape(table)
+    return int(shape[0]) if shape else 0
+
+
+def _psis(log_lik, reff):
+    """(elpd_loo_i, pareto_k_i) float32 device tensors of a table [S, ...] or a dict of such
+    tables, and S."""
+    from . import psis
+
+    if isinstance(log_lik, dict):
+        if not log_lik:
+            raise ValueError("an empty dict of log-likelihood tables")
+        rows = {k: _rows(v) for k, v in log_lik.items()}
+        if len(set(rows.values())) != 1:
+            raise ValueError(f"the log-likelihood tables of one model hold the same samples, got {rows} rows")
+        parts = {k: psis.psis_loo_table(v, reff) for k, v in log_lik.items()}
+        return {k: v[0] for k, v in parts.items()}, {k: v[1] for k, v in parts.items()}, next(iter(rows.values()))
+    elpd, k = psis.psis_loo_table(log_lik, reff)
+    return elpd, k, _rows(log_lik)
+
+
+def pareto_k(log_lik, reff=1.0):
+    """The Pareto-k diagnostic per observation of a log-likelihood table [S, ...] (a dict of tables
+    gives a dict): the shape of the generalised Pareto distribution fitted to the largest
+    leave-one-out importance ratios of the observation, by the PSIS HIP kernel
+    (numpyro_amd/psis.py).  +inf where the tail is too short to fit (at most 4 ratios above the
+    cutoff), NaN for a column that holds a non-finite entry.  A float32 tensor of the table's
+    trailing shape on the current GPU."""
+    return _psis(log_lik, reff)[1]
+
+
+def loo(log_lik, reff=1.0):
+    """Pareto-smoothed importance-sampling leave-one-out cross-validation of a log-likelihood table
+    [S, ...] or a dict of tables (their observations pooled), on the log score scale (Vehtari,
+    Gelman and Gabry 2017): elpd_loo_i from the importance ratios 1 / p(y_i | theta_s), their
+    M = ceil(min(S / 5, 3 sqrt(S / reff))) largest replaced by the order statistics of a fitted
+    generalised Pareto distribution, whose shape k_i is the diagnostic: above k_threshold =
+    min(1 - 1 / log10(S), 0.7) the estimate of that observation is not to be trusted, and a
+    UserWarning says how many there are.  ``reff`` is the relative efficiency of the draws (MCMC
+    effective sample size / S).  Returns {"elpd_loo": sum elpd_loo_i, "p_loo": sum (lppd_i -
+    elpd_loo_i), "lppd": sum lppd_i, "se": sqrt(n var(elpd_loo_i))} (the population variance over
+    the n observations, as waic) as float64 tensors, "elpd_loo_i" and "pareto_k" per observation
+    (float32, shaped like the table's trailing dimensions; dicts for a dict), "k_threshold" and
+    "n_bad".  The per-observation figures come from the PSIS and pointwise HIP kernels, the sums over
+    observations are torch."""
+    import warnings
+
+    import torch
+
+    elpd_i, k_i, S = _psis(log_lik, reff)
+    lp_i = _pointwise(log_lik)[0]
+    if isinstance(elpd_i, dict):
+        elpd = torch.cat([v.reshape(-1) for v in elpd_i.values()])
+        k = torch.cat([v.reshape(-1) for v in k_i.values()])
+        lp = torch.cat([v.reshape(-1) for v in lp_i.values()])
+    else:
+        elpd, k, lp = elpd_i, k_i, lp_i
+    elpd, k, lp = elpd.reshape(-1).double(), k.reshape(-1), lp.reshape(-1).double()
+    n = elpd.numel()
+    k_threshold = min(1.0 - 1.0 / math.log10(S), 0.7)
+    n_bad = int((k > k_threshold).sum())
+    if n_bad > 0:
+        warnings.warn(f"PSIS-LOO: {n_bad} of {n} observations have a Pareto k above {k_threshold:.2f}; elpd_loo of "
+                      "these observations is unreliable", UserWarning, stacklevel=2)
+    return {"elpd_loo": elpd.sum(), "p_loo": (lp - elpd).sum(), "lppd": lp.sum(),
+            "se": torch.sqrt(n * elpd.var(unbiased=False)), "elpd_loo_i": elpd_i, "pareto_k": k_i,
+            "k_threshold": k_threshold, "n_bad": n_bad}

@@ -28,6 +28,8 @@ from ..pointwise import PointwiseReducer
 
 # the tape of one chunk of samples stays under this many bytes
 MAX_WORKSPACE_BYTES = 1 << 30
+# loo holds the whole table and the PSIS kernel's column-contiguous copy of it: both under this
+MAX_LOO_BYTES = 8 << 30
 
 
 def _flatten(model, posterior_samples, batch_ndims, what):
@@ -154,4 +156,40 @@ def pointwise_predictive(model, posterior_samples, *args, batch_ndims=1, **kwarg
         # S equal values: their logsumexp - log S is the value, their variance 0
         c = run.constant(c)
         out[name] = {"lppd": c, "p_waic": torch.full_like(c, 0.0 if S > 1 else float("nan"))}
+    return out
+
+
+def loo(model, posterior_samples, *args, batch_ndims=1, reff=1.0, **kwargs):
+    """{observed site: {"elpd_loo": [*site_shape], "pareto_k": [*site_shape], "lppd": [*site_shape]}}:
+    per observation, the PSIS leave-one-out log predictive density, the Pareto-k diagnostic of its
+    importance ratios (numpyro_amd/psis.py; ``reff`` the relative efficiency of the draws) and the
+    in-sample lppd of ``pointwise_predictive``.  The smoothing needs every sample of an observation
+    at once, so the [S, N] table is held on the device, with the kernel's copy of it."""
+    from .. import psis
+
+    run = _Run(model, posterior_samples, args, kwargs, batch_ndims, "loo")
+    prog, S = run.prog, run.S
+    tail = psis.tail_length(S, reff)
+    psis.check_sizes(S, tail)
+    out = {}
+    if prog.num_ops:
+        N = prog.num_columns
+        need = 4 * S * N + lib().nmx_psis_workspace_bytes(S, N)
+        if need > MAX_LOO_BYTES:
+            raise NotImplementedError(f"loo: the table of S = {S} samples x N = {N} observations and its workspace "
+                                      f"need {need} bytes, above MAX_LOO_BYTES = {MAX_LOO_BYTES}; thin the draws")
+        table = torch.empty(S, N, dtype=torch.float32, device=run.device)
+        for s0, m in run.chunks():
+            run.launch(s0, m, table[s0:])
+        red = PointwiseReducer(N, run.device)
+        red.accumulate(table)
+        lppd, _ = red.finish()
+        elpd, k = psis.psis_loo_columns(table, N, tail)
+        for o in prog.outputs:
+            out[o.name] = {key: v[o.column:o.column + o.n].reshape((o.n,) if o.shape else ()).expand(o.shape).contiguous()
+                           for key, v in (("elpd_loo", elpd), ("pareto_k", k), ("lppd", lppd))}
+    for name, c in prog.constant_outputs.items():
+        # S equal ratios: no tail (T = 0), so no fit, and the estimate is the value itself
+        c = run.constant(c)
+        out[name] = {"elpd_loo": c, "pareto_k": torch.full_like(c, float("inf")), "lppd": c}
     return out

@@ -139,6 +139,8 @@ BINOMIAL_MAX_COUNT = 1 << 24  # NMX_BINOMIAL_MAX_COUNT
 DRAW_MAX_ELEMENTS = 1 << 24  # the counter's element field
 POINTWISE_MAX_SPLITS = 64  # NMX_POINTWISE_MAX_SPLITS
 POINTWISE_MIN_SPLIT_ROWS = 16  # NMX_POINTWISE_MIN_SPLIT_ROWS
+PSIS_MAX_TAIL = 8192  # NMX_PSIS_MAX_TAIL
+PSIS_MAX_ROWS = 1 << 24  # NMX_PSIS_MAX_ROWS
 
 
 class Program(ctypes.Structure):
@@ -204,6 +206,8 @@ SIGNATURES: dict[str, tuple] = {
     "nmx_pointwise_state_bytes": (c_size, [c_int]),
     "nmx_pointwise_accumulate": (c_int, [c_vp, c_int, c_i64, c_int, c_vp, c_int, c_vp]),
     "nmx_pointwise_finish": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp]),
+    "nmx_psis_workspace_bytes": (c_size, [c_int, c_int]),
+    "nmx_psis_loo": (c_int, [c_vp, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "nmx_logreg_packed_bytes": (c_size, [c_i64, c_int]),
     "nmx_logreg_pack": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     "nmx_logreg_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
