@@ -25,6 +25,7 @@ from .. import native
 from .. import potentials as P
 from ..native import check, lib, ptr
 from ..pointwise import PointwiseReducer
+from .predictive import common_batch_shape
 
 # the tape of one chunk of samples stays under this many bytes
 MAX_WORKSPACE_BYTES = 1 << 30
@@ -40,16 +41,14 @@ def _flatten(model, posterior_samples, batch_ndims, what):
         raise NotImplementedError(f"{what}: {model!r} is not a model function")
     if batch_ndims not in (0, 1, 2):
         raise ValueError(f"batch_ndims must be 0, 1 or 2, got {batch_ndims}")
-    batch_shape = proto = None
-    for name, v in posterior_samples.items():
-        shp = tuple(np.shape(v)[:batch_ndims])
-        if len(shp) < batch_ndims:
-            raise ValueError(f"site {name} has shape {tuple(np.shape(v))}, fewer than batch_ndims = {batch_ndims} dimensions")
-        if batch_shape is not None and shp != batch_shape:
-            raise ValueError(f"Batch shapes at site {name} and {proto} should be the same, "
-                             f"but got {shp} and {batch_shape}")
-        if batch_shape is None:
-            batch_shape, proto = shp, name
+
+    def leading():  # (site, batch shape), each checked before the sites after it are looked at
+        for name, v in posterior_samples.items():
+            if np.ndim(v) < batch_ndims:
+                raise ValueError(f"site {name} has shape {tuple(np.shape(v))}, fewer than batch_ndims = {batch_ndims} dimensions")
+            yield name, tuple(np.shape(v)[:batch_ndims])
+
+    batch_shape = common_batch_shape(leading())
     if batch_shape is None:
         raise ValueError("No sample sites in posterior samples to infer `num_samples`.")
     S = int(math.prod(batch_shape))
@@ -69,47 +68,22 @@ class _Run:
 
         flat, self.batch_shape, self.S = _flatten(model, posterior_samples, batch_ndims, what)
         self.prog = prog = compile_log_likelihood(model, args, kwargs, given=flat)
-        for name, _, n, shape in prog.inputs:
-            if tuple(flat[name].shape[1:]) != tuple(shape):
-                raise ValueError(f"posterior samples of site {name!r} have shape {tuple(flat[name].shape[1:])} per "
-                                 f"draw, the model's site has {tuple(shape)}")
-        if torch.cuda.is_available():
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        elif prog.num_ops:
-            raise RuntimeError(f"{what} needs a GPU (the program runs on a HIP kernel)")
-        else:
-            self.device = torch.device("cpu")  # every log density is a host constant
+        self.device = prog.sample_device(flat, what)  # the CPU where every log density is a host constant
         if not prog.num_ops:
             return
-        st, msg = prog.native_check()  # a malformed program never reaches the device
-        if st:
-            raise native.NativeError(f"nmx_loglik_program_check failed (status {st}): {msg}")
-        S, dev = self.S, self.device
-        self.x = (torch.cat([flat[name].to(dev, torch.float32).reshape(S, n) for name, _, n, _ in prog.inputs], 1)
-                  .contiguous() if prog.inputs else None)
-        row_bytes = lib().nmx_predict_program_workspace_bytes(prog.num_slots, 1)
-        self.chunk = min(S, MAX_WORKSPACE_BYTES // row_bytes)
-        if self.chunk <= 0:
-            raise NotImplementedError(f"{what}: one sample's tape of {prog.num_slots} slots needs {row_bytes} bytes, "
-                                      f"above MAX_WORKSPACE_BYTES = {MAX_WORKSPACE_BYTES}")
-        self.d_ops = torch.from_numpy(prog.ops).to(dev)
-        self.d_consts = torch.from_numpy(prog.consts).to(dev)
-        self.d_index = torch.from_numpy(prog.index).to(dev) if prog.index.size else None
-        self.d_outputs = torch.from_numpy(prog.output_table()).to(dev)
-        self.cprog = native.Program(ops=ptr(self.d_ops), consts=ptr(self.d_consts), index=ptr(self.d_index),
-                                    num_ops=prog.num_ops, num_slots=prog.num_slots, num_consts=prog.consts.size,
-                                    num_index=prog.index.size, dim=prog.dim)
-        self.tape = torch.empty(self.chunk, prog.num_slots, dtype=torch.float32, device=dev)
+        self.bound, self.x, self.chunk, self.tape = prog.bind_samples(
+            flat, self.S, self.device, MAX_WORKSPACE_BYTES, what, "MAX_WORKSPACE_BYTES")
+        self.d_outputs = torch.from_numpy(prog.output_table()).to(self.device)
 
     def chunks(self):
         return [(s0, min(self.chunk, self.S - s0)) for s0 in range(0, self.S, self.chunk)]
 
     def launch(self, s0, m, out):
         """Samples [s0, s0 + m) into the rows of ``out`` [>= m, num_columns]."""
-        prog = self.prog
-        check(lib().nmx_loglik_program(ctypes.byref(self.cprog), ptr(self.x[s0:]) if self.x is not None else None, m,
-                                       ptr(self.d_outputs), len(prog.outputs), ptr(self.tape), ptr(out),
-                                       prog.num_columns, native.stream_ptr()), "nmx_loglik_program")
+        prog, x = self.prog, ptr(self.x[s0:]) if self.x is not None else None
+        check(lib().nmx_loglik_program(ctypes.byref(self.bound.struct), x, m, ptr(self.d_outputs), len(prog.outputs),
+                                       ptr(self.tape), ptr(out), prog.num_columns, native.stream_ptr()),
+              "nmx_loglik_program")
 
     def constant(self, c):
         return torch.as_tensor(np.asarray(c, np.float32)).to(self.device)

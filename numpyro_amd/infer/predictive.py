@@ -124,6 +124,18 @@ _PREDICTORS = {
 _HOST_ONLY = {"stochastic_volatility", "funnel", "funnel_reparam"}
 
 
+def common_batch_shape(shapes):
+    """The batch shape that every (site, leading shape) of ``shapes`` has, None without a site."""
+    batch_shape = proto = None
+    for name, shp in shapes:
+        if batch_shape is not None and shp != batch_shape:
+            raise ValueError(f"Batch shapes at site {name} and {proto} should be the same, "
+                             f"but got {shp} and {batch_shape}")
+        if batch_shape is None:
+            batch_shape, proto = shp, name
+    return batch_shape
+
+
 class Predictive:
     """numpyro.infer.Predictive (numpyro/infer/util.py:888-1090) for the fused models and for
     model functions of the program compiler's class (posterior and prior predictive)."""
@@ -153,15 +165,7 @@ class Predictive:
                 raise ValueError(f"num_samples must be positive, got {num_samples}")
             posterior_samples = {}
             batch_ndims = 1
-        batch_shape = None
-        proto = None
-        for name, v in posterior_samples.items():
-            shp = tuple(v.shape[:batch_ndims])
-            if batch_shape is not None and shp != batch_shape:
-                raise ValueError(f"Batch shapes at site {name} and {proto} should be the same, "
-                                 f"but got {shp} and {batch_shape}")
-            if batch_shape is None:
-                batch_shape, proto = shp, name
+        batch_shape = common_batch_shape((k, tuple(v.shape[:batch_ndims])) for k, v in posterior_samples.items())
         if batch_shape is None and (fused or num_samples is None):
             raise ValueError("No sample sites in posterior samples to infer `num_samples`.")
         if batch_shape is None:
@@ -227,16 +231,7 @@ class Predictive:
         nb, S = self.batch_ndims, self.num_samples
         flat = {k: torch.as_tensor(v).reshape(S, *v.shape[nb:]) for k, v in self.posterior_samples.items()}
         prog = compile_predictive(self.model, args, kwargs, given=flat)
-        for name, _, n, shape in prog.inputs:
-            if tuple(flat[name].shape[1:]) != tuple(shape):
-                raise ValueError(f"posterior samples of site {name!r} have shape {tuple(flat[name].shape[1:])} per "
-                                 f"draw, the model's site has {tuple(shape)}")
-        if torch.cuda.is_available():
-            device = torch.device("cuda", torch.cuda.current_device())
-        elif prog.num_ops:
-            raise RuntimeError("Predictive needs a GPU (the program runs on a HIP kernel)")
-        else:
-            device = torch.device("cpu")  # nothing is drawn: observed data / given sites
+        device = prog.sample_device(flat, "Predictive")  # the CPU where nothing is drawn: observed data / given sites
         given = {name: flat[name].to(device, torch.float32) for name, _, _, _ in prog.inputs}
         draws = self._run_program(prog, given, key_to_seed(rng_key), device) if prog.num_ops else {}
         for name, (value, integer) in prog.observed.items():
@@ -260,29 +255,14 @@ class Predictive:
     def _run_program(self, prog, given, seed, device):
         """{output site: [S, *shape]} of the program over all samples, in chunks whose tape stays
         under max_workspace_bytes; a draw depends on the global sample index, not on the chunk."""
-        st, msg = prog.native_check()  # a malformed program never reaches the device
-        if st:
-            raise native.NativeError(f"nmx_predict_program_check failed (status {st}): {msg}")
         S = self.num_samples
-        x = (torch.cat([given[name].reshape(S, n) for name, _, n, _ in prog.inputs], 1).contiguous()
-             if prog.inputs else None)
-        row_bytes = lib().nmx_predict_program_workspace_bytes(prog.num_slots, 1)
-        chunk = min(S, self.max_workspace_bytes // row_bytes)
-        if chunk <= 0:
-            raise NotImplementedError(f"predictive program: one sample's tape of {prog.num_slots} slots needs "
-                                      f"{row_bytes} bytes, above max_workspace_bytes = {self.max_workspace_bytes}")
-        d_ops = torch.from_numpy(prog.ops).to(device)
-        d_consts = torch.from_numpy(prog.consts).to(device)
-        d_index = torch.from_numpy(prog.index).to(device) if prog.index.size else None
-        cprog = native.Program(ops=ptr(d_ops), consts=ptr(d_consts), index=ptr(d_index), num_ops=prog.num_ops,
-                               num_slots=prog.num_slots, num_consts=prog.consts.size, num_index=prog.index.size,
-                               dim=prog.dim)
-        tape = torch.empty(chunk, prog.num_slots, dtype=torch.float32, device=device)
+        bound, x, chunk, tape = prog.bind_samples(given, S, device, self.max_workspace_bytes,
+                                                  "predictive program", "max_workspace_bytes")
         parts = {o.name: [] for o in prog.outputs}
         for s0 in range(0, S, chunk):
             m = min(chunk, S - s0)
-            check(lib().nmx_predict_program(ctypes.byref(cprog), ptr(x[s0:]) if x is not None else None, m, s0, seed,
-                                            ptr(tape), native.stream_ptr()), "nmx_predict_program")
+            check(lib().nmx_predict_program(ctypes.byref(bound.struct), ptr(x[s0:]) if x is not None else None, m, s0,
+                                            seed, ptr(tape), native.stream_ptr()), "nmx_predict_program")
             for o in prog.outputs:
                 v = tape[:m, o.slot:o.slot + o.n]  # a view of the tape: copied out before the next chunk
                 if o.integer:  # whole numbers, or NaN where the parameter is outside the support: -1

@@ -13,21 +13,18 @@ its ``log_prob`` *before* any sum over the site, constants included.  One HIP ke
 the outputs into a dense [S, columns] table; the reduce kernels of the same file turn such a
 table into the pointwise lppd and p_waic without holding it whole.
 
-``LogLikProgram.run_host`` is a NumPy interpreter of the same program (float64; float32 runs the
-same arithmetic in float32, the calibration of the device tests).
+``LogLikProgram.run_host`` runs the same program on the one NumPy forward interpreter (program.py
+``Program._forward_host``; float64, and float32 with the same arithmetic in float32, the
+calibration of the device tests).
 """
 from __future__ import annotations
-
-import ctypes
 
 import numpy as np
 
 from . import distributions as dist
-from . import native
-from .frontend import _base, _host, trace_model
-from .predictive_program import _lgamma
-from .program import (_BINARY, _BINOMIAL, _ELEMENTWISE, _HOST_FWD, _LINALG, _LOGPROB, _SCAN, _UNARY, Program, _Builder,
-                      _Lowering, _Refuse, _ew_mixture, _host_linalg_fwd, _host_scan_fwd, _lp_mvn, _refuse, _V)
+from .frontend import _base, _host
+from .program import (_BINOMIAL, _ELEMENTWISE, _LOGPROB, _ForwardProgram, _Refuse, _ew_mixture, _forward_prologue,
+                      _lp_mvn, _refuse)
 
 
 class LogLikOutput:
@@ -46,16 +43,16 @@ class LogLikOutput:
                 f"{self.column + self.n}) shape {self.shape}")
 
 
-class LogLikProgram(Program):
-    """A forward-only program without draws: slots [0, dim) hold the given sites (``inputs``:
-    (name, offset, n, shape) in sorted name order, constrained values); ``outputs`` are the
+class LogLikProgram(_ForwardProgram):
+    """A forward-only program without draws (program.py _ForwardProgram): ``outputs`` are the
     observed sites whose log density depends on a given site, ``constant_outputs`` (name ->
     float64 array of the site's shape) those that are host constants.  ``num_columns`` is the width
     of the dense table."""
 
+    _CHECK = "nmx_loglik_program_check"
+
     def __init__(self, ops, consts, index, num_slots, dim, inputs, outputs, constant_outputs):
-        super().__init__(ops, consts, index, num_slots, dim)
-        self.inputs, self.outputs = list(inputs), list(outputs)
+        super().__init__(ops, consts, index, num_slots, dim, inputs, outputs)
         self.constant_outputs = dict(constant_outputs)
         self.num_columns = sum(o.n for o in self.outputs)
 
@@ -66,65 +63,15 @@ class LogLikProgram(Program):
 
     def native_check(self, outputs=None, ldo=None):
         """(status, message) of nmx_loglik_program_check on the host arrays: needs no GPU."""
-        lib = native.lib()
-        table = self.output_table() if outputs is None else np.ascontiguousarray(np.asarray(outputs, np.int32))
-        st = lib.nmx_loglik_program_check(ctypes.byref(self.native_struct()),
-                                          int(table.ctypes.data) if table.size else None, table.shape[0],
-                                          self.num_columns if ldo is None else int(ldo))
-        return st, (lib.nmx_last_error().decode(errors="replace") if st else "")
-
-    def op_names(self):
-        return [native.op_name(o) for o in self.ops[:, 0].tolist()]
-
-    def describe(self):
-        return [f"{k}: {nm} dst={o[1]} a={o[2]} b={o[3]} n={o[4]} sa={o[5]} sb={o[6]} aux={o[7]}"
-                for k, (nm, o) in enumerate(zip(self.op_names(), self.ops.tolist()))]
-
-    def flatten_inputs(self, samples, dtype=np.float64):
-        """[S, dim] from a dict name -> [S, *site shape] (or an array [S, dim])."""
-        if isinstance(samples, dict):
-            S = len(next(iter(samples.values())))
-            cols = [np.asarray(samples[name], dtype).reshape(S, n) for name, _, n, _ in self.inputs]
-            return np.concatenate(cols, 1) if cols else np.zeros((S, 0), dtype)
-        return np.atleast_2d(np.asarray(samples, dtype))
+        return super().native_check(outputs, self.num_columns if ldo is None else int(ldo))
 
     # ------------------------------------------------------------------ NumPy interpreter
     def run_host(self, samples, dtype=np.float64):
         """The program on every row of ``samples`` (see flatten_inputs), every op in ``dtype``
         arithmetic: {observed site: [S, *shape]} as ``dtype`` arrays, the constant outputs
         broadcast over S."""
-        T = np.dtype(dtype).type
-        Z = self.flatten_inputs(samples, dtype)
-        S, NS, D = Z.shape[0], self.num_slots, self.dim
-        assert Z.shape[1] == D
-        cp = self.consts64.astype(dtype) if T is np.float64 else self.consts.astype(dtype)
-        ix = self.index
-        v = np.zeros((S, NS), dtype)
-        v[:, :D] = Z
-
-        def operand(ref, n, stride):
-            ln = n if stride else 1
-            return v[:, ref:ref + ln] if ref >= 0 else cp[None, ~ref:~ref + ln]
-
-        fwd = dict(_HOST_FWD, lgamma=lambda x: _lgamma(x, dtype))
-        with np.errstate(all="ignore"):
-            for (op, dst, a, b, n, sa, sb, aux), nm in zip(self.ops.tolist(), self.op_names()):
-                if nm in _UNARY:
-                    v[:, dst:dst + n] = fwd[nm](operand(a, n, sa))
-                elif nm in _BINARY:
-                    v[:, dst:dst + n] = fwd[nm](operand(a, n, sa), operand(b, n, sb))
-                elif nm == "reduce_sum":
-                    v[:, dst] = v[:, a:a + n].sum(1)
-                elif nm == "gather":
-                    v[:, dst:dst + n] = v[:, a + ix[aux:aux + n]]
-                elif nm == "matvec":
-                    M = cp[~b:~b + n * aux].reshape(n, aux)
-                    v[:, dst:dst + n] = v[:, a:a + aux] @ M.T
-                elif nm in _LINALG:
-                    _host_linalg_fwd(nm, v, cp, dst, a, b, n, aux)
-                else:
-                    assert nm in _SCAN, nm
-                    _host_scan_fwd(nm, v, cp, dst, a, b, n, aux)
+        v = self._forward_host(self.flatten_inputs(samples, dtype), dtype, self._pool(dtype))
+        S = v.shape[0]
         out = {o.name: np.broadcast_to(v[:, o.slot:o.slot + o.n].reshape((S,) + ((o.n,) if o.shape else ())),
                                        (S,) + o.shape).copy() for o in self.outputs}
         for name, c in self.constant_outputs.items():
@@ -147,37 +94,16 @@ def compile_log_likelihood(model, args=(), kwargs=None, given=()):
     (sorted by name, constrained values).  A site that is neither observed nor given raises
     ValueError naming it (the reference would need an rng key there); a model outside the program
     compiler's class raises NotImplementedError naming the site."""
-    cfg = getattr(model, "_nmx_reparam", None)
-    fn = getattr(model, "_nmx_model", model)
-    trace = trace_model(fn, args, kwargs, cfg)
-    for name in trace.reparam:
-        _refuse(name, "reparam configs are not supported")
-    given = set(given)
-    sizes = {}
-    for s in trace.sites.values():
-        base = _base(s.fn)
-        if type(base) not in _LOGPROB:
-            _refuse(s.name, f"{type(base).__name__} is not supported")
-        if s.obs is None and s.name not in given:
-            raise ValueError(f"log_likelihood: site {s.name!r} is neither observed nor in the posterior samples "
-                             "(its value would have to be drawn)")
-        if len(s.shape) > 1:
-            _refuse(s.name, f"site of shape {s.shape}: sites of rank > 1 are not supported")
-        if s.obs is not None and np.ndim(_host(s.obs)) > 1:
-            _refuse(s.name, f"observations of shape {np.shape(_host(s.obs))}: rank > 1 is not supported")
-        if s.obs is not None and isinstance(s.fn, dist.Independent):
+    def missing(s, base):
+        raise ValueError(f"log_likelihood: site {s.name!r} is neither observed nor in the posterior samples "
+                         "(its value would have to be drawn)")
+
+    def observed(s):
+        if isinstance(s.fn, dist.Independent):
             _refuse(s.name, "an observed site under to_event: its log density is not elementwise")
-        n = int(np.prod(s.shape, dtype=np.int64))
-        if n <= 0:
-            _refuse(s.name, "empty site")
-        sizes[s.name] = n
-    inputs, dim = [], 0
-    for s in sorted((s for s in trace.sites.values() if s.obs is None), key=lambda s: s.name):
-        inputs.append((s.name, dim, sizes[s.name], tuple(s.shape)))
-        dim += sizes[s.name]
-    B = _Builder(dim)
-    values = {name: _V(B, n, slot=off) for name, off, n, _ in inputs}
-    lower = _Lowering(B, values)
+
+    # every site without data is given (`missing` raises otherwise): they are the inputs
+    trace, _, inputs, B, _, lower = _forward_prologue(model, args, kwargs, given, missing, observed)
     outputs, constant_outputs = [], {}
     for s in trace.sites.values():
         if s.obs is None:
@@ -224,13 +150,9 @@ def compile_log_likelihood(model, args=(), kwargs=None, given=()):
         else:
             outputs.append(LogLikOutput(s.name, total.slot, total.n, shape, 0))
     if not outputs:  # nothing to run on the device: every log density is a host constant
-        return LogLikProgram(np.zeros((0, native.OP_WORDS)), [], [], dim, dim, inputs, [], constant_outputs)
-    made = {op[1]: k for k, op in enumerate(B.ops)}
-    ops, moved, num_slots = B.compact([made[o.slot] for o in outputs if o.slot >= dim])
+        return LogLikProgram.empty(B.dim, inputs, constant_outputs)
     column = 0
     for o in outputs:
-        o.slot = moved.get(o.slot, o.slot)
         o.column = column
         column += o.n
-    consts = np.concatenate(B.consts) if B.consts else np.zeros(0)
-    return LogLikProgram(ops, consts, B.index, num_slots, dim, inputs, outputs, constant_outputs)
+    return LogLikProgram(*B.forward_arrays(outputs), inputs, outputs, constant_outputs)

@@ -15,25 +15,23 @@ One HIP kernel (csrc/predictive_program.hip) runs the program once per posterior
 
 Randomness is the device's Philox stream for predictive draws: element i of sample s of the draw
 op with stream id k (its ordinal in the program) uses the blocks ``words(s, k, i, attempt)``; a
-draw depends only on (seed, sample, stream, element).  ``PredictiveProgram.run_host`` is a NumPy
-interpreter of the same program that defines every draw op word by word (float64; float32 runs
-the same arithmetic in float32, the calibration of the device tests).
+draw depends only on (seed, sample, stream, element).  ``PredictiveProgram.run_host`` runs the same
+program on the one NumPy forward interpreter (program.py ``Program._forward_host``) and hands it
+the draw ops, which are defined here word by word (float64; float32 runs the same arithmetic in
+float32, the calibration of the device tests).
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
 
 from . import distributions as dist
 from . import native
-from .frontend import _base, _host, trace_model
+from .frontend import _base
 from .jnp import Sym, shape_of
-from .program import (_BINARY, _HOST_FWD, _LINALG, _LOGPROB, _SCAN, _UNARY, Program, _Builder, _Lowering, _Refuse,
-                      _host_linalg_fwd, _host_scan_fwd, _refuse, _V)
+from .program import _LOGPROB, _ForwardProgram, _Refuse, _forward_prologue, _operand, _refuse
 
-_DRAW_NAME = {v: k for k, v in native.DRAW_OPCODE.items()}
 _U24 = 5.9604644775390625e-08  # 2^-24
 
 
@@ -176,16 +174,16 @@ def _sym_latents(x, out):
     return out
 
 
-class PredictiveProgram(Program):
-    """A forward-only program: slots [0, dim) hold the given sites (``inputs``: (name, offset,
-    n, shape) in sorted name order, constrained values), ``outputs`` the drawn sites and the
-    deterministic sites that depend on one; ``observed`` the sites that keep their data (name ->
-    (data, integer?)) and
-    ``host_deterministics`` the deterministic expressions of given sites alone."""
+class PredictiveProgram(_ForwardProgram):
+    """A forward-only program with draw ops (program.py _ForwardProgram): ``outputs`` are the drawn
+    sites and the deterministic sites that depend on one; ``observed`` the sites that keep their data
+    (name -> (data, integer?)) and ``host_deterministics`` the deterministic expressions of given
+    sites alone."""
+
+    _CHECK = "nmx_predict_program_check"
 
     def __init__(self, ops, consts, index, num_slots, dim, inputs, outputs, observed, host_deterministics):
-        super().__init__(ops, consts, index, num_slots, dim)
-        self.inputs, self.outputs = list(inputs), list(outputs)
+        super().__init__(ops, consts, index, num_slots, dim, inputs, outputs)
         self.observed, self.host_deterministics = dict(observed), dict(host_deterministics)
 
     @property
@@ -194,32 +192,6 @@ class PredictiveProgram(Program):
 
     def output_table(self):
         return np.ascontiguousarray(np.asarray([[o.slot, o.n] for o in self.outputs], np.int32).reshape(-1, 2))
-
-    def native_check(self, outputs=None):
-        """(status, message) of nmx_predict_program_check on the host arrays: needs no GPU."""
-        lib = native.lib()
-        table = self.output_table() if outputs is None else np.ascontiguousarray(np.asarray(outputs, np.int32))
-        st = lib.nmx_predict_program_check(ctypes.byref(self.native_struct()),
-                                           int(table.ctypes.data) if table.size else None, table.shape[0])
-        return st, (lib.nmx_last_error().decode(errors="replace") if st else "")
-
-    def op_names(self):
-        return [_DRAW_NAME[o] if o >= native.DRAW_BASE else native.op_name(o) for o in self.ops[:, 0].tolist()]
-
-    def describe(self):
-        return [f"{k}: {nm} dst={o[1]} a={o[2]} b={o[3]} n={o[4]} sa={o[5]} sb={o[6]} aux={o[7]}"
-                for k, (nm, o) in enumerate(zip(self.op_names(), self.ops.tolist()))]
-
-    def flatten_inputs(self, samples, dtype=np.float64):
-        """[S, dim] from a dict name -> [S, *site shape] (or an array [S, dim], or S when dim = 0)."""
-        if isinstance(samples, (int, np.integer)):
-            assert self.dim == 0, "a sample count alone needs a program without given sites"
-            return np.zeros((int(samples), 0), dtype)
-        if isinstance(samples, dict):
-            S = len(next(iter(samples.values())))
-            cols = [np.asarray(samples[name], dtype).reshape(S, n) for name, _, n, _ in self.inputs]
-            return np.concatenate(cols, 1) if cols else np.zeros((S, 0), dtype)
-        return np.atleast_2d(np.asarray(samples, dtype))
 
     # ------------------------------------------------------------------ NumPy interpreter
     def run_host(self, samples, seed, words, dtype=np.float64, sample_offset=0, info=None):
@@ -232,58 +204,28 @@ class PredictiveProgram(Program):
         [S, n]} of every draw op (-1: none).  The draw ops are defined here word by word; the
         kernel's header (csrc/nmx_program.h, include/numpyro_amd.h) states the same assignment."""
         T = np.dtype(dtype).type
-        Z = self.flatten_inputs(samples, dtype)
-        S, NS, D = Z.shape[0], self.num_slots, self.dim
-        assert Z.shape[1] == D
-        cp = self.consts64.astype(dtype) if T is np.float64 else self.consts.astype(dtype)
-        ix = self.index
-        v = np.zeros((S, NS), dtype)
-        v[:, :D] = Z
+        Z, cp = self.flatten_inputs(samples, dtype), self._pool(dtype)
+        S = Z.shape[0]
         rows = (np.arange(S, dtype=np.int64) + int(sample_offset))[:, None]
-
-        def operand(ref, n, stride):
-            ln = n if stride else 1
-            return v[:, ref:ref + ln] if ref >= 0 else cp[None, ~ref:~ref + ln]
 
         def blocks(stream, n, attempt):
             return np.asarray(words(seed, rows, stream, np.arange(n, dtype=np.int64)[None, :], attempt), np.uint32)
 
-        fwd = dict(_HOST_FWD, lgamma=lambda x: _lgamma(x, dtype))
-        with np.errstate(all="ignore"):
-            for (op, dst, a, b, n, sa, sb, aux), nm in zip(self.ops.tolist(), self.op_names()):
-                if nm in _UNARY:
-                    v[:, dst:dst + n] = fwd[nm](operand(a, n, sa))
-                elif nm in _BINARY:
-                    v[:, dst:dst + n] = fwd[nm](operand(a, n, sa), operand(b, n, sb))
-                elif nm == "reduce_sum":
-                    v[:, dst] = v[:, a:a + n].sum(1)
-                elif nm == "gather":
-                    v[:, dst:dst + n] = v[:, a + ix[aux:aux + n]]
-                elif nm == "matvec":
-                    M = cp[~b:~b + n * aux].reshape(n, aux)
-                    v[:, dst:dst + n] = v[:, a:a + aux] @ M.T
-                elif nm in _SCAN:
-                    _host_scan_fwd(nm, v, cp, dst, a, b, n, aux)
-                elif nm in _LINALG:
-                    _host_linalg_fwd(nm, v, cp, dst, a, b, n, aux)
-                else:
-                    par = None if nm in _NO_PARAM else np.broadcast_to(operand(a, n, sa), (S, n))
-                    if nm == "draw_binomial":
-                        par = (par, np.broadcast_to(operand(b, n, sb), (S, n)))
-                    steps = {}
-                    out, att = _host_draw(nm, par, lambda t, k=aux, m=n: blocks(k, m, t), (S, n), T, steps)
-                    v[:, dst:dst + n] = out
-                    if info is not None:
-                        info[aux] = att
-                        if steps:  # the inversion walk's step count per element (binomial)
-                            info[("steps", aux)] = steps["steps"]
+        def draw(nm, op, v):
+            _, dst, a, b, n, sa, sb, aux = op
+            par = None if nm in _NO_PARAM else np.broadcast_to(_operand(v, cp, a, n, sa), (S, n))
+            if nm == "draw_binomial":
+                par = (par, np.broadcast_to(_operand(v, cp, b, n, sb), (S, n)))
+            steps = {}
+            out, att = _host_draw(nm, par, lambda t: blocks(aux, n, t), (S, n), T, steps)
+            v[:, dst:dst + n] = out
+            if info is not None:
+                info[aux] = att
+                if steps:  # the inversion walk's step count per element (binomial)
+                    info[("steps", aux)] = steps["steps"]
+
+        v = self._forward_host(Z, dtype, cp, draw)
         return {o.name: v[:, o.slot:o.slot + o.n].reshape((S,) + o.shape).copy() for o in self.outputs}
-
-
-def _lgamma(x, dtype):
-    import torch
-
-    return torch.lgamma(torch.as_tensor(np.ascontiguousarray(x, dtype))).numpy()
 
 
 def _u01(x, T):
@@ -516,39 +458,16 @@ def compile_predictive(model, args=(), kwargs=None, given=()):
     sample sites without data whose name is in ``given`` are the inputs (sorted by name,
     constrained values); every other site without data is drawn.  Raises NotImplementedError
     naming the site for a model outside the program compiler's class."""
-    cfg = getattr(model, "_nmx_reparam", None)
-    fn = getattr(model, "_nmx_model", model)
-    trace = trace_model(fn, args, kwargs, cfg)
-    for name in trace.reparam:
-        _refuse(name, "reparam configs are not supported")
-    given = set(given)
-    sizes = {}
-    for s in trace.sites.values():
-        base = _base(s.fn)
-        if type(base) not in _LOGPROB:
-            _refuse(s.name, f"{type(base).__name__} is not supported")
-        if type(base) in _UNDRAWABLE and s.obs is None and s.name not in given:
-            if isinstance(base, dist.MultivariateNormal):
-                _refuse(s.name, "drawing a MultivariateNormal site is not supported (predictive programs have no "
-                                "product of a factor with a drawn vector): pass its data, or leave the site out of "
-                                "the model")
+    def drawn(s, base):  # a site that has neither data nor a given value
+        if isinstance(base, dist.MultivariateNormal):
+            _refuse(s.name, "drawing a MultivariateNormal site is not supported (predictive programs have no "
+                            "product of a factor with a drawn vector): pass its data, or leave the site out of "
+                            "the model")
+        if type(base) in _UNDRAWABLE:
             _refuse(s.name, f"drawing a {type(base).__name__} site needs a data-dependent index, which predictive "
                             "programs do not have: pass its data, or leave the site out of the model")
-        if len(s.shape) > 1:
-            _refuse(s.name, f"site of shape {s.shape}: sites of rank > 1 are not supported")
-        if s.obs is not None and np.ndim(_host(s.obs)) > 1:
-            _refuse(s.name, f"observations of shape {np.shape(_host(s.obs))}: rank > 1 is not supported")
-        n = int(np.prod(s.shape, dtype=np.int64))
-        if n <= 0:
-            _refuse(s.name, "empty site")
-        sizes[s.name] = n
-    inputs, dim = [], 0
-    for s in sorted((s for s in trace.sites.values() if s.obs is None and s.name in given), key=lambda s: s.name):
-        inputs.append((s.name, dim, sizes[s.name], tuple(s.shape)))
-        dim += sizes[s.name]
-    B = _Builder(dim)
-    values = {name: _V(B, n, slot=off) for name, off, n, _ in inputs}
-    lower = _Lowering(B, values)
+
+    trace, sizes, inputs, B, values, lower = _forward_prologue(model, args, kwargs, given, drawn)
     outputs, observed = [], {}
     for s in trace.sites.values():
         if s.obs is not None:
@@ -584,14 +503,9 @@ def compile_predictive(model, args=(), kwargs=None, given=()):
             _refuse(name, f"deterministic site of shape {shape}: rank > 1 is not supported")
         val = lower(expr, name)
         outputs.append(Output(name, val.slot, val.n, shape, False))
-    if not outputs:
-        # nothing to run on the device: every site is given or observed
-        return PredictiveProgram(np.zeros((0, native.OP_WORDS)), [], [], dim, dim, inputs, [], observed, host_dets)
-    made = {op[1]: k for k, op in enumerate(B.ops)}
-    ops, moved, num_slots = B.compact([made[o.slot] for o in outputs])
-    for o in outputs:
-        o.slot = moved[o.slot]
+    if not outputs:  # nothing to run on the device: every site is given or observed
+        return PredictiveProgram.empty(B.dim, inputs, observed, host_dets)
+    prog = PredictiveProgram(*B.forward_arrays(outputs), inputs, outputs, observed, host_dets)
     # stream ids are ordinals both before and after compaction: every draw feeds an output site
-    assert [op[7] for op in ops if op[0] >= native.DRAW_BASE] == list(range(B.n_draws))
-    consts = np.concatenate(B.consts) if B.consts else np.zeros(0)
-    return PredictiveProgram(ops, consts, B.index, num_slots, dim, inputs, outputs, observed, host_dets)
+    assert prog.ops[prog.ops[:, 0] >= native.DRAW_BASE, 7].tolist() == list(range(B.n_draws))
+    return prog

@@ -15,7 +15,9 @@ Host passes: subexpressions without a latent are folded in float64 into the cons
 (every normalising constant ends there), common subexpressions are shared (a ``Sym`` used twice
 is one value), ``log(exp(x))`` is ``x``, ``log1p(-x)`` of a unit-interval site's own value is
 ``-softplus(u)``.  ``Program.run_host`` is a float64 NumPy interpreter
-of the same program, forward and reverse: it defines the kernel's semantics op by op.
+of the same program, forward and reverse: it defines the kernel's semantics op by op.  Its forward
+pass, ``Program._forward_host``, is the one forward interpreter of every program kind: the
+predictive and log-likelihood programs (``_ForwardProgram``) run it in float64 and float32.
 
 Model class: latent sites of rank 0 or 1 with support ``real``, ``positive`` (the kernel
 sees u = log x and the program adds -sum(u), as NmxEightSchools does), ``unit_interval`` /
@@ -56,10 +58,13 @@ _UNARY = ("neg", "exp", "log", "sqrt", "tanh", "log1p", "square", "softplus", "l
 _BINARY = ("add", "sub", "mul", "div", "pow")
 
 
-def _lgamma64(x):
+_DRAW_NAME = {v: k for k, v in native.DRAW_OPCODE.items()}
+
+
+def _lgamma(x, dtype=np.float64):
     import torch
 
-    return torch.lgamma(torch.as_tensor(np.asarray(x, np.float64))).numpy()
+    return torch.lgamma(torch.as_tensor(np.require(x, dtype, "C"))).numpy()
 
 
 def _digamma64(x):
@@ -71,7 +76,7 @@ def _digamma64(x):
 _HOST_FWD = {
     "neg": lambda x: -x, "exp": np.exp, "log": np.log, "sqrt": np.sqrt, "tanh": np.tanh, "log1p": np.log1p,
     "square": np.square, "softplus": lambda x: np.maximum(x, 0.0) + np.log1p(np.exp(-np.abs(x))),
-    "lgamma": _lgamma64,
+    "lgamma": _lgamma,
     "add": np.add, "sub": np.subtract, "mul": np.multiply, "div": np.divide, "pow": np.power,
 }
 
@@ -105,6 +110,12 @@ def _host_rev(op, gd, x, y, out):
     if op == "div":
         return gd / y, -(gd * out) / y
     return gd * (y * np.power(x, y - 1.0)), gd * (out * np.log(x))  # pow
+
+
+def _operand(v, cp, ref, n, stride):
+    """An elementwise op's operand: n tape slots (one where the stride is 0) or constants (ref < 0)."""
+    ln = n if stride else 1
+    return v[:, ref:ref + ln] if ref >= 0 else cp[None, ~ref:~ref + ln]
 
 
 def _host_logsumexp(x):
@@ -265,42 +276,43 @@ class Program:
         return native.Program(ops=p(ops), consts=p(consts), index=p(index), num_ops=ops.shape[0],
                               num_slots=self.num_slots, num_consts=consts.size, num_index=index.size, dim=self.dim)
 
-    def native_check(self):
-        """(status, message) of nmx_program_check on the host arrays: needs no GPU."""
+    _CHECK = "nmx_program_check"  # the library's check of this kind of program
+
+    def native_check(self, *extra):
+        """(status, message) of the kind's check (``_CHECK``) on the host arrays: needs no GPU."""
         lib = native.lib()
-        st = lib.nmx_program_check(ctypes.byref(self.native_struct()))
+        st = getattr(lib, self._CHECK)(ctypes.byref(self.native_struct()), *extra)
         return st, (lib.nmx_last_error().decode(errors="replace") if st else "")
 
+    def upload(self, device):
+        """This program checked and on ``device``: a _DeviceProgram."""
+        return _DeviceProgram(self, device)
+
+    def op_names(self):
+        return [_DRAW_NAME[o] if o >= native.DRAW_BASE else native.op_name(o) for o in self.ops[:, 0].tolist()]
+
     def describe(self):
-        return [f"{k}: {native.op_name(o[0])} dst={o[1]} a={o[2]} b={o[3]} n={o[4]} sa={o[5]} sb={o[6]} aux={o[7]}"
-                for k, o in enumerate(self.ops.tolist())]
+        return [f"{k}: {nm} dst={o[1]} a={o[2]} b={o[3]} n={o[4]} sa={o[5]} sb={o[6]} aux={o[7]}"
+                for k, (nm, o) in enumerate(zip(self.op_names(), self.ops.tolist()))]
 
-    # ------------------------------------------------------------------ float64 interpreter
-    def run_host(self, Z, f32_consts=False):
-        """(U [C], dU/dz [C, D]) of the rows of Z [C, D], in float64: the program forward and
-        reverse, op by op as the kernel runs it (only the order inside sums differs).
-        ``f32_consts``: with the constant pool rounded to float32, as the device holds it."""
-        Z = np.atleast_2d(np.asarray(Z, np.float64))
-        C, S, D = Z.shape[0], self.num_slots, self.dim
-        assert Z.shape[1] == D
-        cp = self.consts.astype(np.float64) if f32_consts else self.consts64
+    # ------------------------------------------------------------------ NumPy interpreter
+    def _forward_host(self, Z, dtype, cp, draw=None):
+        """The tape v [rows, num_slots] of the rows of Z [rows, dim]: every op forward in ``dtype``
+        arithmetic over the constant pool ``cp``, op by op as the kernels run it (only the order inside
+        sums differs).  ``draw(name, op words, v)`` fills a draw op's slots (predictive programs).  The
+        one forward interpreter of the three program kinds: an op it does not know is an error."""
+        assert Z.shape[1] == self.dim
+        v = np.zeros((Z.shape[0], self.num_slots), dtype)
+        v[:, :self.dim] = Z
         ix = self.index
-        v = np.zeros((C, S))
-        g = np.zeros((C, S))
-        v[:, :D] = Z
-
-        def operand(ref, n, stride):
-            ln = n if stride else 1
-            return v[:, ref:ref + ln] if ref >= 0 else cp[None, ~ref:~ref + ln]
-
-        ops = self.ops.tolist()
+        fwd = dict(_HOST_FWD, lgamma=lambda x: _lgamma(x, dtype))
         with np.errstate(all="ignore"):
-            for op, dst, a, b, n, sa, sb, aux in ops:
-                nm = native.op_name(op)
+            for o, nm in zip(self.ops.tolist(), self.op_names()):
+                op, dst, a, b, n, sa, sb, aux = o
                 if nm in _UNARY:
-                    v[:, dst:dst + n] = _HOST_FWD[nm](operand(a, n, sa))
+                    v[:, dst:dst + n] = fwd[nm](_operand(v, cp, a, n, sa))
                 elif nm in _BINARY:
-                    v[:, dst:dst + n] = _HOST_FWD[nm](operand(a, n, sa), operand(b, n, sb))
+                    v[:, dst:dst + n] = fwd[nm](_operand(v, cp, a, n, sa), _operand(v, cp, b, n, sb))
                 elif nm == "reduce_sum":
                     v[:, dst] = v[:, a:a + n].sum(1)
                 elif nm == "gather":
@@ -310,15 +322,31 @@ class Program:
                     v[:, dst:dst + n] = v[:, a:a + aux] @ M.T
                 elif nm in _LINALG:
                     _host_linalg_fwd(nm, v, cp, dst, a, b, n, aux)
-                else:
+                elif nm in _SCAN:
                     _host_scan_fwd(nm, v, cp, dst, a, b, n, aux)
-            g[:, S - 1] = 1.0
-            for op, dst, a, b, n, sa, sb, aux in reversed(ops):
+                else:
+                    assert op >= native.DRAW_BASE and draw is not None, nm
+                    draw(nm, o, v)
+        return v
+
+    def run_host(self, Z, f32_consts=False):
+        """(U [C], dU/dz [C, D]) of the rows of Z [C, D], in float64: the program forward
+        (_forward_host) and reverse, op by op as the kernel runs it.
+        ``f32_consts``: with the constant pool rounded to float32, as the device holds it."""
+        Z = np.atleast_2d(np.asarray(Z, np.float64))
+        C, S, D = Z.shape[0], self.num_slots, self.dim
+        cp = self.consts.astype(np.float64) if f32_consts else self.consts64
+        ix = self.index
+        v = self._forward_host(Z, np.float64, cp)
+        g = np.zeros((C, S))
+        g[:, S - 1] = 1.0
+        with np.errstate(all="ignore"):
+            for op, dst, a, b, n, sa, sb, aux in reversed(self.ops.tolist()):
                 nm = native.op_name(op)
                 gd = g[:, dst:dst + (1 if nm == "reduce_sum" else n)]
                 if nm in _UNARY or nm in _BINARY:
-                    x = operand(a, n, sa)
-                    y = operand(b, n, sb) if nm in _BINARY else None
+                    x = _operand(v, cp, a, n, sa)
+                    y = _operand(v, cp, b, n, sb) if nm in _BINARY else None
                     da, db = _host_rev(nm, gd, x, y, v[:, dst:dst + n])
                     for ref, stride, d in ((a, sa, da), (b, sb, db)):
                         if d is None or ref < 0:
@@ -385,6 +413,93 @@ class Program:
             el += sum(src) + nd  # forward
             el += nd + sum(src) + nd + 2 * sum(src)  # reverse: adjoint in, operands, result, adjoints +=
         return 4 * el
+
+
+class _DeviceProgram:
+    """A program's arrays on a device and the nmx_program over them (``struct``).  A malformed program
+    never reaches the device; the tensors live as long as this object, so keep it while the struct's
+    pointers are in use."""
+
+    def __init__(self, prog, device):
+        import torch
+
+        st, msg = prog.native_check()
+        if st:
+            raise native.NativeError(f"{prog._CHECK} failed (status {st}): {msg}")
+        self.d_ops = torch.from_numpy(prog.ops).to(device)
+        self.d_consts = torch.from_numpy(prog.consts).to(device)
+        self.d_index = torch.from_numpy(prog.index).to(device) if prog.index.size else None
+        self.struct = native.Program(ops=native.ptr(self.d_ops), consts=native.ptr(self.d_consts),
+                                     index=native.ptr(self.d_index), num_ops=prog.num_ops, num_slots=prog.num_slots,
+                                     num_consts=prog.consts.size, num_index=prog.index.size, dim=prog.dim)
+
+
+class _ForwardProgram(Program):
+    """A forward-only program run once per sample (predictive_program.py, loglik_program.py): slots
+    [0, dim) hold the given sites, ``inputs``: (name, offset, n, shape) in sorted name order,
+    constrained values; ``outputs`` name tape slots (each kind has its own output_table)."""
+
+    def __init__(self, ops, consts, index, num_slots, dim, inputs, outputs):
+        super().__init__(ops, consts, index, num_slots, dim)
+        self.inputs, self.outputs = list(inputs), list(outputs)
+
+    @classmethod
+    def empty(cls, dim, inputs, *rest):
+        """The program with nothing to run on the device (no op, no output)."""
+        return cls(np.zeros((0, native.OP_WORDS)), [], [], dim, dim, inputs, [], *rest)
+
+    def native_check(self, outputs=None, *extra):
+        """(status, message) of the kind's check on the host arrays and an output table (default:
+        this program's): needs no GPU."""
+        table = self.output_table() if outputs is None else np.ascontiguousarray(np.asarray(outputs, np.int32))
+        return super().native_check(int(table.ctypes.data) if table.size else None, table.shape[0], *extra)
+
+    def flatten_inputs(self, samples, dtype=np.float64):
+        """[S, dim] from a dict name -> [S, *site shape] (or an array [S, dim], or S when dim = 0)."""
+        if isinstance(samples, (int, np.integer)):
+            assert self.dim == 0, "a sample count alone needs a program without given sites"
+            return np.zeros((int(samples), 0), dtype)
+        if isinstance(samples, dict):
+            S = len(next(iter(samples.values())))
+            cols = [np.asarray(samples[name], dtype).reshape(S, n) for name, _, n, _ in self.inputs]
+            return np.concatenate(cols, 1) if cols else np.zeros((S, 0), dtype)
+        return np.atleast_2d(np.asarray(samples, dtype))
+
+    def _pool(self, dtype):
+        """The constant pool of run_host in ``dtype``: the float64 one, else the device's float32 one."""
+        return self.consts64 if np.dtype(dtype) == np.float64 else self.consts.astype(dtype)
+
+    # ------------------------------------------------------------------ device
+    def sample_device(self, flat, what):
+        """The device this program runs on for the samples ``flat`` {site: [S, *shape]}, whose
+        shapes per draw must be the model's: the current GPU; the CPU for a program without ops."""
+        import torch
+
+        for name, _, n, shape in self.inputs:
+            if tuple(flat[name].shape[1:]) != tuple(shape):
+                raise ValueError(f"posterior samples of site {name!r} have shape {tuple(flat[name].shape[1:])} per "
+                                 f"draw, the model's site has {tuple(shape)}")
+        if torch.cuda.is_available():
+            return torch.device("cuda", torch.cuda.current_device())
+        if self.num_ops:
+            raise RuntimeError(f"{what} needs a GPU (the program runs on a HIP kernel)")
+        return torch.device("cpu")
+
+    def bind_samples(self, flat, S, device, max_bytes, what, limit):
+        """(the uploaded program, x [S, dim] float32 of the samples ``flat`` or None without inputs,
+        the samples per launch, their tape [chunk, num_slots]) on ``device``, the tape under
+        ``max_bytes``; the refusal names the caller ``what`` and its ``limit``."""
+        import torch
+
+        bound = self.upload(device)
+        x = (torch.cat([flat[name].to(device, torch.float32).reshape(S, n) for name, _, n, _ in self.inputs], 1)
+             .contiguous() if self.inputs else None)
+        row_bytes = native.lib().nmx_predict_program_workspace_bytes(self.num_slots, 1)
+        chunk = min(S, max_bytes // row_bytes)
+        if chunk <= 0:
+            raise NotImplementedError(f"{what}: one sample's tape of {self.num_slots} slots needs {row_bytes} bytes, "
+                                      f"above {limit} = {max_bytes}")
+        return bound, x, chunk, torch.empty(chunk, self.num_slots, dtype=torch.float32, device=device)
 
 
 # ------------------------------------------------------------------------------------------
@@ -593,9 +708,23 @@ class _Builder:
 
     def program(self):
         """The ops the last one (U) depends on, renumbered so that each defines the next free slots."""
-        out, _, cursor = self.compact([len(self.ops) - 1])
+        return Program(*self.arrays([len(self.ops) - 1])[0])
+
+    def arrays(self, roots):
+        """((ops, consts, index, num_slots, dim), old slot -> new slot) of compact(roots): the
+        leading arguments of a Program."""
+        ops, moved, num_slots = self.compact(roots)
         consts = np.concatenate(self.consts) if self.consts else np.zeros(0)
-        return Program(out, consts, self.index, cursor, self.dim)
+        return (ops, consts, self.index, num_slots, self.dim), moved
+
+    def forward_arrays(self, outputs):
+        """The Program arguments of the ops that the output sites depend on; the outputs' slots are
+        renumbered with the ops (an output that is a given site's own slots keeps them)."""
+        made = {op[1]: k for k, op in enumerate(self.ops)}
+        arrays, moved = self.arrays([made[o.slot] for o in outputs if o.slot >= self.dim])
+        for o in outputs:
+            o.slot = moved.get(o.slot, o.slot)
+        return arrays
 
     def compact(self, roots):
         """(ops, old slot -> new slot, num_slots) of the ops that the ops `roots` depend on,
@@ -1060,13 +1189,50 @@ class _Lowering:
         return self.B.gather(v, idx)
 
 
-def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
-    """Trace ``model(*args, **kwargs)`` and lower its potential to a ProgramPotential."""
-    cfg = getattr(model, "_nmx_reparam", None)
-    fn = getattr(model, "_nmx_model", model)
-    trace = trace_model(fn, args, kwargs, cfg)
+def _trace(model, args, kwargs):
+    """The trace of ``model(*args, **kwargs)``, a reparam wrapper unwrapped; reparam configs are refused."""
+    trace = trace_model(getattr(model, "_nmx_model", model), args, kwargs, getattr(model, "_nmx_reparam", None))
     for name in trace.reparam:
         _refuse(name, "reparam configs are not supported")
+    return trace
+
+
+def _forward_prologue(model, args, kwargs, given, missing, observed=lambda s: None):
+    """The start of compile_predictive and compile_log_likelihood: the trace, the per-site checks,
+    the given sites without data laid out as inputs in sorted name order, and a builder over them:
+    (trace, sizes, inputs, B, values, lower).  ``missing(s, base)`` sees a site that has neither
+    data nor a given value, ``observed(s)`` a site with data once its shape has passed."""
+    trace = _trace(model, args, kwargs)
+    given = set(given)
+    sizes = {}
+    for s in trace.sites.values():
+        base = _base(s.fn)
+        if type(base) not in _LOGPROB:
+            _refuse(s.name, f"{type(base).__name__} is not supported")
+        if s.obs is None and s.name not in given:
+            missing(s, base)
+        if len(s.shape) > 1:
+            _refuse(s.name, f"site of shape {s.shape}: sites of rank > 1 are not supported")
+        if s.obs is not None:
+            if np.ndim(_host(s.obs)) > 1:
+                _refuse(s.name, f"observations of shape {np.shape(_host(s.obs))}: rank > 1 is not supported")
+            observed(s)
+        n = int(np.prod(s.shape, dtype=np.int64))
+        if n <= 0:
+            _refuse(s.name, "empty site")
+        sizes[s.name] = n
+    inputs, dim = [], 0
+    for s in sorted((s for s in trace.sites.values() if s.obs is None and s.name in given), key=lambda s: s.name):
+        inputs.append((s.name, dim, sizes[s.name], tuple(s.shape)))
+        dim += sizes[s.name]
+    B = _Builder(dim)
+    values = {name: _V(B, n, slot=off) for name, off, n, _ in inputs}
+    return trace, sizes, inputs, B, values, _Lowering(B, values)
+
+
+def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
+    """Trace ``model(*args, **kwargs)`` and lower its potential to a ProgramPotential."""
+    trace = _trace(model, args, kwargs)
     lat = sorted((s for s in trace.sites.values() if s.obs is None), key=lambda s: s.name)
     if not lat:
         raise _Refuse("program compiler: the model has no latent sample sites")
@@ -1210,22 +1376,14 @@ class ProgramPotential(Potential):
         import torch
 
         prog = self.program
-        # a malformed program never reaches the device
-        st, msg = prog.native_check()
-        if st:
-            raise native.NativeError(f"nmx_program_check failed (status {st}): {msg}")
+        device_program = prog.upload(device)
         wb = native.lib().nmx_pe_program_workspace_bytes(prog.num_slots, ldc)
         if wb > self.max_workspace_bytes:
             raise NotImplementedError(
                 f"program potential: the tape of {prog.num_slots} slots for {C} chains (ldc {ldc}) needs a workspace "
                 f"of {wb} bytes, above max_workspace_bytes = {self.max_workspace_bytes}; run fewer chains per engine")
-        self.d_ops = torch.from_numpy(prog.ops).to(device)
-        self.d_consts = torch.from_numpy(prog.consts).to(device)
-        self.d_index = torch.from_numpy(prog.index).to(device) if prog.index.size else None
         self.workspace = torch.empty(wb, dtype=torch.uint8, device=device)
-        self._cprog = native.Program(ops=native.ptr(self.d_ops), consts=native.ptr(self.d_consts),
-                                     index=native.ptr(self.d_index), num_ops=prog.num_ops, num_slots=prog.num_slots,
-                                     num_consts=prog.consts.size, num_index=prog.index.size, dim=prog.dim)
+        self._device_program, self._cprog = device_program, device_program.struct  # the holder keeps the arrays
 
     def evaluate(self, ev, stream):
         native.check(native.lib().nmx_pe_program(ctypes.byref(self._cprog), ctypes.byref(ev),

@@ -12,8 +12,32 @@ import numpy as np
 import pytest
 
 import program_op_cases as OC
+from numpyro_amd import native
 from numpyro_amd.program import Program
 from test_gpu_program import G_TOL, U_TOL
+
+
+def test_the_forward_interpreter_knows_every_op():
+    """One op per opcode name at n = 2 (a 2 x 2 matrix for the dense ops) through the one forward
+    interpreter: an arithmetic op fills its slots, a draw op goes to the callback and is an error
+    without one."""
+    Z = np.array([[3.0, 0.5, 0.25, 1.5, 0.75, 1.25]])
+    pool = [1.0, 2.0, 3.0, 4.0, 1.0, 3.0, 2.0, 4.0]  # a matvec's M, then its transpose
+    layout = {"cholesky": (4, 0, 2), "trisolve": (2, 4, 0), "matvec": (2, ~0, 2), "logsumexp": (2, 0, 2),
+              "concat": (2, 2, 1)}  # (n, b, aux) where they are not (2, z[2:4], 0)
+    for name in native.OPCODES + native.LINALG_OPCODES + native.DRAW_OPCODES:
+        n, b, aux = layout.get(name, (2, 2, 0))
+        code = native.DRAW_OPCODE[name] if name in native.DRAW_OPCODE else native.OPCODE[name]
+        p = Program([[code, 6, 0, b, n, 1, 1, aux]], pool, [1, 0], 10, 6)
+        assert p.op_names() == [name]
+        seen = []
+        v = p._forward_host(Z, np.float64, p.consts64, lambda nm, op, v: seen.append((nm, op)))
+        if name in native.DRAW_OPCODES:
+            assert seen == [(name, p.ops[0].tolist())]
+            with pytest.raises(AssertionError):
+                p._forward_host(Z, np.float64, p.consts64)
+        else:
+            assert not seen and np.all(np.isfinite(v)) and np.any(v[0, 6:] != 0.0), (name, v)
 
 
 @pytest.mark.parametrize("family", OC.FAMILIES)
