@@ -9,16 +9,13 @@
 #pragma once
 #include <math.h>
 
-// NMX_SV_FAST (default): the SV row's q / (1 + q) by the hardware reciprocal and log1p(q) as
-// log(u) q / (u - 1), u = 1 + q, from the hardware log2 -- a few ulp instead of the libm forms'
-// ~1, 62 instead of 177 VALU instructions per row.  The persistent SV kernel is VALU-bound
+// The SV row's q / (1 + q) is by the hardware reciprocal and its log1p(q) is log(u) q / (u - 1),
+// u = 1 + q, from the hardware log2 -- a few ulp instead of the libm forms' ~1, 62 instead of 177
+// VALU instructions per row.  The persistent SV kernel is VALU-bound
 // (profiles/r04/sv_persistent_pmc_and_bc.txt): 29.9M -> 35.6M leapfrog/s at 8192 chains, 14.1M ->
-// 18.1M at 1024 (profiles/r04/ab_sv_row_math.txt).  Every schedule includes this header, so they
-// stay bitwise equal to each other; against the float64 oracle the potential keeps its tolerance.
-#ifndef NMX_SV_FAST
-#define NMX_SV_FAST 1
-#endif
-
+// 18.1M at 1024 against the libm forms (profiles/r04/ab_sv_row_math.txt).  Every schedule includes
+// this header, so they stay bitwise equal to each other; against the float64 oracle the potential
+// keeps its tolerance.
 #include "nmx_common.h"
 
 // A double constant materialized at its use: the compiler otherwise hoists the 64-bit constants
@@ -146,7 +143,8 @@ struct NmxWideSV {
   // dU/ds_t of row d = 1 + t (GaussianRandomWalk stencil + StudentT(nu, 0, e^s) term)
   // (off: byte offset of the row; ldc4: the byte stride between rows -- 4 ldc in the
   // chain-minor layout, 4 in the chain-row layout of the persistent wide kernel).  row_load /
-  // row_eval split row() into its loads and its arithmetic (the pipelined leaf, nuts.hip).
+  // row_eval split row() into its loads and its arithmetic (the persistent kernel's carry form
+  // batches the loads of several rows, nuts.hip).
   struct RowIn {
     float s, sp, sn, r;
   };
@@ -177,18 +175,12 @@ struct NmxWideSV {
     const float dd = s - sp;
     const float dn = t + 1 < T ? sn - s : 0.0f;
     const float r = x.r;
-#if NMX_SV_FAST
     const float q = r * r * nmx_expf_unchecked(-2.0f * s) * g.inv_nu;
     const float u = 1.0f + q;
     const float qq = q * __builtin_amdgcn_rcpf(u);
     const float l1q = (u == 1.0f || !(u < INFINITY)) ? q
                                                      : __builtin_amdgcn_logf(u) * 0.6931471805599453f *
                                                            (q * __builtin_amdgcn_rcpf(u - 1.0f));
-#else
-    const float q = r * r * expf(-2.0f * s) * g.inv_nu;
-    const float qq = q / (1.0f + q);
-    const float l1q = log1pf(q);
-#endif
     sums[0] += dd * dd;
     sums[1] += l1q;
     sums[2] += qq;

@@ -30,9 +30,38 @@ namespace {
 constexpr int MAXD = NMX_MAX_TREE_DEPTH;
 constexpr int NPART = 2 * MAXD + 3;  // KE, checkpoint dots (2 per level), whole-tree dots
 constexpr int WIDE_MIN_D = 257;      // D from which the step runs D-split (wide schedule)
+
+// ---- tunables (each with its evidence; -D overrides one for scripts/ab_build.py) ------------
 #ifndef NMX_STEP_CPW
 #define NMX_STEP_CPW 16
 #endif
+#ifndef NMX_V2_WAVES
+#define NMX_V2_WAVES 4  // waves per k_wide_v2 block
+#endif
+#ifndef NMX_V2_BATCH
+#define NMX_V2_BATCH 2  // rows of a momentum block per load round in k_wide_v2 (measurement at its use)
+#endif
+#ifndef NMX_LEAF_OCC
+#define NMX_LEAF_OCC 3  // waves per SIMD k_wide_leaf is compiled for (4: <= 128 VGPRs, small spills, slower)
+#endif
+#ifndef NMX_PX_B
+#define NMX_PX_B 2  // rows per thread in flight in the persistent wide kernel (profiles/r03/ab_persistent_occ.txt)
+#endif
+#ifndef NMX_PX_BA
+// rows per thread in flight in the persistent wide kernel's apply phase: SV 8192 chains 1 / 2 / 3 /
+// 4 rows 42.7 / 41.9 / 39.7 / 33.9M (profiles/r06/sv_phase_stamps.txt: fewer values live across the
+// phase's LDS round trips)
+#define NMX_PX_BA 1
+#endif
+#ifndef NMX_PX_BC
+// rows per batch of the carry form's leaf rows: SV 8192 chains 2 / 3 / 4 rows 40.0 / 40.0 / 40.3M
+// (before the apply loop's fix), 3 / 4 / 5: 42.5 / 42.7 / 42.8M (profiles/r06/sv_phase_stamps.txt)
+#define NMX_PX_BC 4
+#endif
+#ifndef NMX_PX_OCC
+#define NMX_PX_OCC 4  // waves per SIMD k_wide_persistent is compiled for: <= 128 VGPRs (3 waves: SV 8192 20.0M vs 24.2M)
+#endif
+
 constexpr int STEP_CPW = NMX_STEP_CPW;  // chains per wave of the fused step (TPC = 8, D >= 16)
 constexpr int SMALL_CPW = 16;        // chains per wave of the one-wave step (D < 16) and persistent kernel
 
@@ -813,26 +842,8 @@ __device__ __forceinline__ void leaf_store(const VecCtx& v, const Act& A, float 
 template <bool NUTS, int ROWS, bool PRE1 = (ROWS == 2)>
 __device__ __forceinline__ void leaf_rows(const VecCtx& v, const Act& A, float seff, int d0, int d1, int step, int c,
                                           float* red) {
+  static_assert(ROWS == 1 || ROWS == 2, "one or two rows per load round");
   int d = d0;
-  if constexpr (ROWS == 3) {
-    // software-pipelined: the next row's loads are issued before this row's stores, so two
-    // rows' loads are in flight through the whole loop (one row per round leaves the memory
-    // pipe idle while a row computes and stores)
-    if (d >= d1) return;
-    LeafIn cur;
-    uint32_t ic = nmx_row_off(d, v.ldc, c);
-    leaf_load<NUTS, true>(v, A, ic, cur);
-    for (; d < d1; d += step) {
-      const int dn = d + step;
-      const uint32_t in = nmx_row_off(dn, v.ldc, c);
-      LeafIn nxt;
-      if (dn < d1) leaf_load<NUTS, true>(v, A, in, nxt);
-      leaf_store<NUTS, true>(v, A, seff, ic, cur, red);
-      cur = nxt;
-      ic = in;
-    }
-    return;
-  }
   if constexpr (ROWS == 2) {
     for (; d + step < d1; d += 2 * step) {
       LeafIn x0, x1;
@@ -1155,18 +1166,13 @@ __device__ __forceinline__ void fused_step(PA P, float* lds, int* wait_go = null
   float red[NPART];
 #pragma unroll
   for (int i = 0; i < NPART; ++i) red[i] = 0.0f;
-// two rows per load round in the leaf and apply phases (a lane holds <= 2 rows at D <= 64):
-// every row's loads go out before the first row's stores, whose completion the next row's
-// loads would otherwise wait for (vmcnt counts stores and loads in issue order); step kernel
-// p50 21.0 -> 19.9 us in the 512-chain covtype protocol, bitwise the same draws (round 5)
-#ifndef NMX_STEP_LROWS
-#define NMX_STEP_LROWS 2
-#endif
-#ifndef NMX_STEP_AROWS
-#define NMX_STEP_AROWS 2
-#endif
-  constexpr int LROWS = TPC > 1 ? (NMX_STEP_LROWS == 2 ? 2 : 1) : 1;
-  constexpr bool LPRE = TPC > 1 && NMX_STEP_LROWS >= 1;
+  // TPC > 1: two rows per load round in the leaf and apply phases (a lane holds <= 2 rows at
+  // D <= 64): every row's loads go out before the first row's stores, whose completion the next
+  // row's loads would otherwise wait for (vmcnt counts stores and loads in issue order); step
+  // kernel p50 21.0 -> 19.9 us in the 512-chain covtype protocol, bitwise the same draws (round 5,
+  // profiles/r03/ab_step_rows.txt)
+  constexpr int LROWS = TPC > 1 ? 2 : 1;
+  constexpr bool LPRE = TPC > 1;
   if (A.leaf) {
     if (is_nuts) leaf_rows<true, LROWS, LPRE>(v, A, seff, vw, D, NV, c, red);
     else leaf_rows<false, LROWS, LPRE>(v, A, seff, vw, D, NV, c, red);
@@ -1186,8 +1192,8 @@ __device__ __forceinline__ void fused_step(PA P, float* lds, int* wait_go = null
   if (vec2) {
     float* const samp = (A.slot >= 0 && P.samples) ? P.samples + (size_t)A.slot * D * ldc : nullptr;
     const float step_eff = S.step_eff;
-    if constexpr (TPC > 1 && NMX_STEP_AROWS >= 1) {
-      ke0[0] = apply_rows<NMX_STEP_AROWS>(v, A, step_eff, vw, NV, c, seed, gch, S.it, samp, P.transform, cfg);
+    if constexpr (TPC > 1) {
+      ke0[0] = apply_rows<2>(v, A, step_eff, vw, NV, c, seed, gch, S.it, samp, P.transform, cfg);
     } else {
       for (int blk = vw; 4 * blk < D; blk += NV) {
         float n[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1301,26 +1307,8 @@ __global__ __launch_bounds__(64 * WIDE_WAVES) void k_wide_v1(WideArgs W) {
   if (A.leaf) {
     // one row per round with the row's checkpoints loaded ahead: 114 VGPRs, 4 waves per SIMD
     // (rows in pairs: 134 VGPRs, 3 waves; SV launched -2.4%, funnel-10k diag -3.5%)
-#ifndef NMX_PX_B
-#define NMX_PX_B 2  // rows per thread in flight in the persistent wide kernel (profiles/r03/ab_persistent_occ.txt)
-#endif
-#ifndef NMX_PX_FAST_APPLY
-#define NMX_PX_FAST_APPLY 1  // the persistent wide kernel's mid-trajectory apply loop (persist_apply_prep_rows)
-#endif
-#ifndef NMX_PX_BA
-// rows per thread in flight in the persistent wide kernel's apply phase: SV 8192 chains 1 / 2 / 3 /
-// 4 rows 42.7 / 41.9 / 39.7 / 33.9M (profiles/r06/sv_phase_stamps.txt: fewer values live across the
-// phase's LDS round trips)
-#define NMX_PX_BA 1
-#endif
-#ifndef NMX_PX_BL
-#define NMX_PX_BL NMX_PX_B  // the same in its leaf phase
-#endif
-#ifndef NMX_V1_ROWS
-#define NMX_V1_ROWS 1
-#endif
-    if (is_nuts) leaf_rows<true, NMX_V1_ROWS, true>(v, A, seff, d0 + wv, d1, WIDE_WAVES, c, red);
-    else leaf_rows<false, NMX_V1_ROWS, true>(v, A, seff, d0 + wv, d1, WIDE_WAVES, c, red);
+    if (is_nuts) leaf_rows<true, 1, true>(v, A, seff, d0 + wv, d1, WIDE_WAVES, c, red);
+    else leaf_rows<false, 1, true>(v, A, seff, d0 + wv, d1, WIDE_WAVES, c, red);
   }
   block_sum<WIDE_WAVES, NPART>(red, lds);
   if (wv == 0 && A.leaf) {
@@ -1420,12 +1408,6 @@ __global__ __launch_bounds__(64) void k_wide_s(WideArgs W) {
   end_step(cfg, a, c, valid, ph_in, S, A);
 }
 
-#ifndef NMX_V2_WAVES
-#define NMX_V2_WAVES 4
-#endif
-#ifndef NMX_V2_BATCH
-#define NMX_V2_BATCH 2
-#endif
 constexpr int V2_WAVES = NMX_V2_WAVES;  // waves per V2 block: each takes momentum blocks wv, wv + V2_WAVES, ...
 
 __global__ __launch_bounds__(64 * V2_WAVES) void k_wide_v2(WideArgs W) {
@@ -1518,36 +1500,6 @@ __device__ __forceinline__ void leaf_rows_model(const VecCtx& v, const Act& A, c
   float* GE = AV(NMX_F_G_EVAL);
   int d = d0;
   const uint32_t ldc4 = (uint32_t)v.ldc << 2;
-#ifndef NMX_LEAF_PIPE
-#define NMX_LEAF_PIPE 0
-#endif
-  if constexpr (NMX_LEAF_PIPE) {
-    // software-pipelined as leaf_rows<ROWS = 3>: the next row's leaf state and model inputs
-    // are loaded before this row's model arithmetic and stores
-    if (d >= d1) return;
-    LeafIn cur;
-    typename M::RowIn mc;
-    uint32_t ic = nmx_row_off(d, v.ldc, c);
-    leaf_load<NUTS, true, false>(v, A, ic, cur);
-    m.row_load(ZE, ic, ldc4, d, mc);
-    for (; d < d1; d += step) {
-      const int dn = d + step;
-      const uint32_t in = nmx_row_off(dn, v.ldc, c);
-      LeafIn nxt;
-      typename M::RowIn mn;
-      if (dn < d1) {
-        leaf_load<NUTS, true, false>(v, A, in, nxt);
-        m.row_load(ZE, in, ldc4, dn, mn);
-      }
-      cur.g = m.row_eval(mc, d, gl, sums);
-      nmx_at(GE, ic) = cur.g;
-      leaf_store<NUTS, true>(v, A, seff, ic, cur, red);
-      cur = nxt;
-      mc = mn;
-      ic = in;
-    }
-    return;
-  }
   for (; d < d1; d += step) {
     const uint32_t i0 = nmx_row_off(d, v.ldc, c);
     LeafIn x0;
@@ -1558,9 +1510,6 @@ __device__ __forceinline__ void leaf_rows_model(const VecCtx& v, const Act& A, c
   }
 }
 
-#ifndef NMX_LEAF_OCC
-#define NMX_LEAF_OCC 3  // waves per SIMD k_wide_leaf is compiled for (4: <= 128 VGPRs, small spills, slower)
-#endif
 template <class M>
 __global__ __launch_bounds__(64 * WIDE_WAVES, NMX_LEAF_OCC) void k_wide_leaf(WideArgs W, M m, float* ppart) {
   constexpr int NR = NPART + M::NSUM;
@@ -1875,17 +1824,6 @@ __device__ __forceinline__ int first_row(const M& m) {
   return d0;
 }
 
-#ifndef NMX_PX_PIPE
-// persist_leaf_rows_carry software-pipelined over two batches (A/B: 55.6-56.1M with two buffers of
-// 2 rows vs 57.2-57.5M unpipelined at SV 8192 chains -- the other chains' waves already cover the
-// store drain; profiles/r06/sv_phase_stamps.txt)
-#define NMX_PX_PIPE 0
-#endif
-#ifndef NMX_PX_BC
-// rows per batch of the carry form's leaf rows: SV 8192 chains 2 / 3 / 4 rows 40.0 / 40.0 / 40.3M
-// (before the apply loop's fix), 3 / 4 / 5: 42.5 / 42.7 / 42.8M (profiles/r06/sv_phase_stamps.txt)
-#define NMX_PX_BC 4
-#endif
 struct PRowG {
   float rs_old, rst, ro, ckr, ckrs;
 };
@@ -1959,33 +1897,15 @@ __device__ __forceinline__ void persist_leaf_rows_carry(const VecCtx& v, const A
       }
     }
   };
-#if NMX_PX_PIPE
-  // software-pipelined over two register buffers: batch b + 1's loads go out before batch b's
-  // stores, so the wait for them does not also wait for those stores (loads and stores share
-  // vmcnt, in order) -- one batch per memory round instead of a full store drain per batch
-  PRowG xa[BC], xb[BC];
-  typename M::RowIn ma[BC], mb[BC];
-  int d0 = first_row(m);
-  if (d0 < hi) load(d0, xa, ma);
-  while (d0 < hi) {
-    int d1 = d0 + BC * NT;
-    if (d1 < hi) load(d1, xb, mb);
-    compute(d0, xa, ma);
-    d0 = d1;
-    if (d0 >= hi) break;
-    d1 = d0 + BC * NT;
-    if (d1 < hi) load(d1, xa, ma);
-    compute(d0, xb, mb);
-    d0 = d1;
-  }
-#else
+  // one batch at a time: software-pipelined over two register buffers of 2 rows this loop measured
+  // 55.6-56.1M against 57.2-57.5M at SV 8192 chains -- the other chains' waves already cover the
+  // store drain (profiles/r06/sv_phase_stamps.txt)
   for (int d0 = first_row(m); d0 < hi; d0 += BC * NT) {
     PRowG xg[BC];
     typename M::RowIn mi[BC];
     load(d0, xg, mi);
     compute(d0, xg, mi);
   }
-#endif
   red[0] += acc[0];
   red[1 + 2 * MAXD] += acc[1];
   red[2 + 2 * MAXD] += acc[2];
@@ -2293,9 +2213,15 @@ __device__ __forceinline__ void spre_leaf(const VecCtx& v, const Act& A, float s
   }
 }
 
-#ifndef NMX_PX_OCC
-#define NMX_PX_OCC 4  // waves per SIMD the kernel is compiled for: <= 128 VGPRs (3 waves: SV 8192 20.0M vs 24.2M)
-#endif
+// The persistent wide kernel's serial section (wave 0: the potential's finish and the NUTS
+// scalar logic, while the chain's other waves wait at a barrier) runs at raised wave priority, so
+// the SIMD's arbiter issues it ahead of the row work of the other chains' waves sharing the SIMD
+// (their phases are throughput-bound; the serial section is the chain's critical path).
+__device__ __forceinline__ void nmx_serial_prio(bool on) {
+  if (on) __builtin_amdgcn_s_setprio(3);
+  else __builtin_amdgcn_s_setprio(0);
+}
+
 // k_wide_persistent's static LDS, one struct (no padding between arrays; persist_carry sizes the
 // carry form's dynamic LDS by it).  lds: the leaf's wave sums.  The chain's scalar state lives in
 // LDS: wave 0 runs the scalar logic on it and publishes the decisions the vector phases need
@@ -2306,20 +2232,6 @@ __device__ __forceinline__ void spre_leaf(const VecCtx& v, const Act& A, float s
 // keeps the first three in lds itself (wave 0 writes them after its lanes read every wave sum;
 // the KE sums after the scalar logic, with a barrier before the next leaf's wave sums) and the
 // prefetched inputs in wave 0's registers.
-// The persistent wide kernel's serial section (wave 0: the potential's finish and the NUTS
-// scalar logic, while the chain's other waves wait at a barrier) runs at raised wave priority, so
-// the SIMD's arbiter issues it ahead of the row work of the other chains' waves sharing the SIMD
-// (their phases are throughput-bound; the serial section is the chain's critical path).
-#ifndef NMX_PX_PRIO
-#define NMX_PX_PRIO 1
-#endif
-__device__ __forceinline__ void nmx_serial_prio(bool on) {
-#if NMX_PX_PRIO
-  if (on) __builtin_amdgcn_s_setprio(3);
-  else __builtin_amdgcn_s_setprio(0);
-#endif
-}
-
 template <int NT, class M, bool CARRY>
 struct PersistShared {
   static constexpr int NW = NT / 64, NR = NPART + M::NSUM;
@@ -2441,8 +2353,8 @@ __global__ __launch_bounds__(NT, NMX_PX_OCC) void k_wide_persistent(StepArgs Pk,
           if (is_nuts) persist_leaf_rows_carry<true, NT, NMX_PX_BC>(v, A, m, gl, seff, base, red, fr);
           else persist_leaf_rows_carry<false, NT, NMX_PX_BC>(v, A, m, gl, seff, base, red, fr);
         } else {
-          if (is_nuts) persist_leaf_rows<true, NT, NMX_PX_BL, CARRY>(v, A, m, gl, seff, base, red, fr);
-          else persist_leaf_rows<false, NT, NMX_PX_BL, CARRY>(v, A, m, gl, seff, base, red, fr);
+          if (is_nuts) persist_leaf_rows<true, NT, NMX_PX_B, CARRY>(v, A, m, gl, seff, base, red, fr);
+          else persist_leaf_rows<false, NT, NMX_PX_B, CARRY>(v, A, m, gl, seff, base, red, fr);
         }
         wave_sums_to_lds<NW, NR>(red, lds, A, is_nuts);
       }
@@ -2543,7 +2455,7 @@ __global__ __launch_bounds__(NT, NMX_PX_OCC) void k_wide_persistent(StepArgs Pk,
       float ke0 = 0.0f;
       constexpr int RARE = ACT_DONE_SUB | ACT_TAKE_BIASED | ACT_HMC_ACCEPT | ACT_ITER_DONE | ACT_WF_UPDATE |
                            ACT_FINALIZE | ACT_START;
-      if (CARRY && NMX_PX_FAST_APPLY && (act & ACT_PREP) && !(act & RARE) && D2.new_dir == D2.dirR) {
+      if (CARRY && (act & ACT_PREP) && !(act & RARE) && D2.new_dir == D2.dirR) {
         persist_apply_prep_rows<NT>(v, D2, m, uni_f(Ssh.step_eff), base, fr);
       } else if (act & VEC) {
         float* const samp = (D2.iter_done && D2.slot >= 0 && P.samples) ? P.samples + (size_t)D2.slot * D * ldc
@@ -2753,7 +2665,7 @@ __global__ __launch_bounds__(NT, NMX_PX_OCC) void k_chain_step(StepArgs Pk) {
   float ke0 = 0.0f;
   constexpr int RARE = ACT_DONE_SUB | ACT_TAKE_BIASED | ACT_HMC_ACCEPT | ACT_ITER_DONE | ACT_WF_UPDATE |
                        ACT_FINALIZE | ACT_START;
-  if (NMX_PX_FAST_APPLY && (act & ACT_PREP) && !(act & RARE) && D2.new_dir == D2.dirR) {
+  if ((act & ACT_PREP) && !(act & RARE) && D2.new_dir == D2.dirR) {
     apply_prep_rows_arena<NT, B>(v, D2, rows, uni_f(sh_seff), base);
   } else if (act & VEC) {
     float* const samp = (D2.iter_done && D2.slot >= 0 && P.samples) ? P.samples + (size_t)D2.slot * D * ldc : nullptr;
@@ -3037,6 +2949,85 @@ Arena arena_of(const nmx_nuts_config* cfg, void* base) {
 // fused schedule only (D < WIDE_MIN_D)
 int tpc_for_dim(int D) { return D < 16 ? 1 : 8; }
 
+// the collection buffers of a stepping entry point (samples may be NULL: the per-transition
+// fields alone are collected)
+int need_collection(const nmx_nuts_config* cfg, const float* fields, const int8_t* transform) {
+  if (cfg->collection_size > 0 && (!fields || !transform))
+    return nmx_fail(NMX_ERR_INVALID, "collection buffers are NULL");
+  return NMX_OK;
+}
+
+// the per-chain kernels (chain-row arena) address a field by 32-bit byte offsets
+int need_field_below_4g(const nmx_nuts_config* cfg, const char* what) {
+  if ((size_t)cfg->ldc * cfg->dim * 4 > 0xFFFFFFF0ull)
+    return nmx_fail(NMX_ERR_INVALID, "%s: a vector field exceeds 4 GiB", what);
+  return NMX_OK;
+}
+
+StepArgs step_args(const nmx_nuts_config* cfg, void* arena, float* samples, float* fields,
+                   const int8_t* transform) {
+  StepArgs args;
+  args.a = arena_of(cfg, arena);
+  args.cfg = *cfg;
+  args.samples = samples;
+  args.fields = fields;
+  args.transform = transform;
+  return args;
+}
+
+// Builds the D-split model `model` (nmx_wide_models.h) after its shape checks and returns f(m);
+// entry prefixes the messages.  funnel_min2: the caller also refuses a funnel of n < 2.
+template <class F>
+int with_wide_model(const char* entry, const nmx_nuts_config* cfg, int model, const float* data, int n,
+                    bool funnel_min2, F&& f) {
+  const bool funnel_ok = n == cfg->dim && !(funnel_min2 && n < 2);
+  const char* const min2 = funnel_min2 ? " >= 2" : "";
+  switch (model) {
+    case NMX_WIDE_STOCHASTIC_VOLATILITY:
+      if (!data || n <= 1 || n + 2 != cfg->dim)
+        return nmx_fail(NMX_ERR_INVALID, "%s: stochastic volatility needs returns[T], dim == T + 2", entry);
+      return f(NmxWideSV{data, n});
+    case NMX_WIDE_FUNNEL:
+      if (!funnel_ok) return nmx_fail(NMX_ERR_INVALID, "%s: funnel needs n == dim%s", entry, min2);
+      return f(NmxWideFunnel{n});
+    case NMX_WIDE_FUNNEL_NONCENTERED:
+      if (!funnel_ok) return nmx_fail(NMX_ERR_INVALID, "%s: funnel_noncentered needs n == dim%s", entry, min2);
+      return f(NmxWideFunnelNC{n});
+    default:
+      return nmx_fail(NMX_ERR_INVALID, "%s: unknown model %d", entry, model);
+  }
+}
+
+// threads per chain of the persistent wide kernel, from dim only (the sums' order depends on
+// it).  The NMX_PERSIST_NT environment override for kernel experiments exists only in the debug
+// build and in experiment builds (-DNMX_EXPERIMENT, scripts/ab_build.py): the release library's
+// results never depend on the environment.
+int persist_nt(int dim) {
+#if defined(NMX_DEBUG) || defined(NMX_EXPERIMENT)
+  if (const char* e = getenv("NMX_PERSIST_NT")) {
+    const int v = atoi(e);
+    if (v == 128 || v == 256 || v == 512 || v == 1024) return v;
+  }
+#endif
+  // SV (D = 2519): 256 -> 13.1M leapfrog/s at 8192 chains, 512 -> 9.6M; funnel-10k: 512 -> 5.1M,
+  // 256 -> 4.7M (profiles/r03/ab_persistent_nt.txt)
+  return dim <= 4096 ? 256 : 512;
+}
+
+// f(std::integral_constant<int, NT>) for nt = persist_nt(dim): the per-chain kernels are compiled
+// for the thread counts persist_nt can return, so 128 and 1024 only beside its override
+template <class F>
+int with_persist_nt(int nt, F&& f) {
+  switch (nt) {
+#if defined(NMX_DEBUG) || defined(NMX_EXPERIMENT)
+    case 128: return f(std::integral_constant<int, 128>{});
+    case 1024: return f(std::integral_constant<int, 1024>{});
+#endif
+    case 256: return f(std::integral_constant<int, 256>{});
+    default: return f(std::integral_constant<int, 512>{});
+  }
+}
+
 }  // namespace
 
 extern "C" int nmx_nuts_num_slices(int dim) { return num_slices(dim); }
@@ -3168,19 +3159,12 @@ extern "C" int nmx_nuts_run_small(const nmx_nuts_config* cfg, void* arena, float
   if ((st = need_chain_minor(cfg, "nmx_nuts_run_small"))) return st;
   if (group_count(*cfg) > 1) return nmx_fail(NMX_ERR_INVALID, "nmx_nuts_run_small: one chain group only");
   if (!arena) return nmx_fail(NMX_ERR_INVALID, "arena is NULL");
-  // samples may be NULL: the per-transition fields alone are collected
-  if (cfg->collection_size > 0 && (!fields || !transform))
-    return nmx_fail(NMX_ERR_INVALID, "collection buffers are NULL");
+  if ((st = need_collection(cfg, fields, transform))) return st;
   if (tpc_for_dim(cfg->dim) != 1 || num_slices(cfg->dim) != 0)
     return nmx_fail(NMX_ERR_INVALID, "run_small: dim %d is not a one-wave model (dim < 16)", cfg->dim);
   if (cfg->sync_chains) return nmx_fail(NMX_ERR_INVALID, "run_small: the persistent schedule is per-chain async");
   if (!p0 || !p1 || max_steps <= 0) return nmx_fail(NMX_ERR_INVALID, "run_small: bad model parameters");
-  StepArgs args;
-  args.a = arena_of(cfg, arena);
-  args.cfg = *cfg;
-  args.samples = samples;
-  args.fields = fields;
-  args.transform = transform;
+  const StepArgs args = step_args(cfg, arena, samples, fields, transform);
   const dim3 grid((cfg->num_chains + SMALL_CPW - 1) / SMALL_CPW), blk(64);
   hipStream_t s = (hipStream_t)stream;
   if (model == NMX_SMALL_DIAG_NORMAL) {
@@ -3197,7 +3181,6 @@ extern "C" int nmx_nuts_run_small(const nmx_nuts_config* cfg, void* arena, float
 }
 
 namespace {
-int persist_nt(int dim);
 // nmx_nuts_step on a chain-row arena: the per-chain step kernel (D-split dims only)
 int step_chain_rows(const nmx_nuts_config* cfg, void* arena, float* samples, float* fields, const int8_t* transform,
                     void* stream) {
@@ -3205,25 +3188,17 @@ int step_chain_rows(const nmx_nuts_config* cfg, void* arena, float* samples, flo
     return nmx_fail(NMX_ERR_INVALID, "step: the chain-row layout is for dim >= %d", WIDE_MIN_D);
   if (group_count(*cfg) > 1) return nmx_fail(NMX_ERR_INVALID, "step: chain-row layout, one chain group only");
   if (cfg->parity != 0 && cfg->parity != 1) return nmx_fail(NMX_ERR_INVALID, "parity must be 0 or 1");
-  if (cfg->collection_size > 0 && (!fields || !transform))
-    return nmx_fail(NMX_ERR_INVALID, "collection buffers are NULL");
-  if ((size_t)cfg->ldc * cfg->dim * 4 > 0xFFFFFFF0ull)
-    return nmx_fail(NMX_ERR_INVALID, "step: a vector field exceeds 4 GiB");
-  StepArgs args;
-  args.a = arena_of(cfg, arena);
-  args.cfg = *cfg;
-  args.samples = samples;
-  args.fields = fields;
-  args.transform = transform;
+  int st;
+  if ((st = need_collection(cfg, fields, transform))) return st;
+  if ((st = need_field_below_4g(cfg, "step"))) return st;
+  const StepArgs args = step_args(cfg, arena, samples, fields, transform);
   const dim3 grid(cfg->num_chains);
   hipStream_t s = (hipStream_t)stream;
-  switch (persist_nt(cfg->dim)) {
-    case 128: hipLaunchKernelGGL((k_chain_step<128, NMX_PX_B>), grid, dim3(128), 0, s, args); break;
-    case 256: hipLaunchKernelGGL((k_chain_step<256, NMX_PX_B>), grid, dim3(256), 0, s, args); break;
-    case 512: hipLaunchKernelGGL((k_chain_step<512, NMX_PX_B>), grid, dim3(512), 0, s, args); break;
-    default: hipLaunchKernelGGL((k_chain_step<1024, NMX_PX_B>), grid, dim3(1024), 0, s, args);
-  }
-  return nmx_check_launch("k_chain_step");
+  return with_persist_nt(persist_nt(cfg->dim), [&](auto nt) {
+    constexpr int NT = decltype(nt)::value;
+    hipLaunchKernelGGL((k_chain_step<NT, NMX_PX_B>), grid, dim3(NT), 0, s, args);
+    return nmx_check_launch("k_chain_step");
+  });
 }
 }  // namespace
 
@@ -3233,21 +3208,14 @@ extern "C" int nmx_nuts_step(const nmx_nuts_config* cfg, void* arena, float* sam
   if (st) return st;
   if (!arena) return nmx_fail(NMX_ERR_INVALID, "arena is NULL");
   if (cfg->layout == NMX_LAYOUT_CHAIN_ROWS) return step_chain_rows(cfg, arena, samples, fields, transform, stream);
-  // samples may be NULL: the per-transition fields alone are collected
-  if (cfg->collection_size > 0 && (!fields || !transform))
-    return nmx_fail(NMX_ERR_INVALID, "collection buffers are NULL");
-  StepArgs args;
-  args.a = arena_of(cfg, arena);
-  args.cfg = *cfg;
-  args.samples = samples;
-  args.fields = fields;
-  args.transform = transform;
-  const int grid = cfg->ldc / 64;
-  hipStream_t s = (hipStream_t)stream;
+  if ((st = need_collection(cfg, fields, transform))) return st;
   if (cfg->parity != 0 && cfg->parity != 1) return nmx_fail(NMX_ERR_INVALID, "parity must be 0 or 1");
   const int ns = num_slices(cfg->dim);
   if (ns > 0 && group_count(*cfg) > 1)
     return nmx_fail(NMX_ERR_INVALID, "chain groups: the fused step only (dim <= 256)");
+  const StepArgs args = step_args(cfg, arena, samples, fields, transform);
+  const int grid = cfg->ldc / 64;
+  hipStream_t s = (hipStream_t)stream;
   if (ns > 0) {
     WideArgs w{args, ns, slice_width(cfg->dim)};
     hipLaunchKernelGGL(k_wide_v1, dim3(grid, ns), dim3(64 * WIDE_WAVES), 0, s, w);
@@ -3294,54 +3262,17 @@ extern "C" int nmx_nuts_step_wide_model(const nmx_nuts_config* cfg, void* arena,
   if ((st = need_chain_minor(cfg, "nmx_nuts_step_wide_model"))) return st;
   if (group_count(*cfg) > 1) return nmx_fail(NMX_ERR_INVALID, "nmx_nuts_step_wide_model: one chain group only");
   if (!arena || !workspace) return nmx_fail(NMX_ERR_INVALID, "arena / workspace is NULL");
-  // samples may be NULL: the per-transition fields alone are collected
-  if (cfg->collection_size > 0 && (!fields || !transform))
-    return nmx_fail(NMX_ERR_INVALID, "collection buffers are NULL");
+  if ((st = need_collection(cfg, fields, transform))) return st;
   const int ns = num_slices(cfg->dim);
   if (ns == 0) return nmx_fail(NMX_ERR_INVALID, "step_wide_model: dim %d uses the fused step (dim < %d)", cfg->dim,
                                WIDE_MIN_D);
-  StepArgs args;
-  args.a = arena_of(cfg, arena);
-  args.cfg = *cfg;
-  args.samples = samples;
-  args.fields = fields;
-  args.transform = transform;
-  const WideArgs w{args, ns, slice_width(cfg->dim)};
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  switch (model) {
-    case NMX_WIDE_STOCHASTIC_VOLATILITY:
-      if (!data || n <= 1 || n + 2 != cfg->dim)
-        return nmx_fail(NMX_ERR_INVALID, "step_wide_model: stochastic volatility needs returns[T], dim == T + 2");
-      return launch_wide_model(w, NmxWideSV{data, n}, ws, cfg->ldc, s);
-    case NMX_WIDE_FUNNEL:
-      if (n != cfg->dim) return nmx_fail(NMX_ERR_INVALID, "step_wide_model: funnel needs n == dim");
-      return launch_wide_model(w, NmxWideFunnel{n}, ws, cfg->ldc, s);
-    case NMX_WIDE_FUNNEL_NONCENTERED:
-      if (n != cfg->dim) return nmx_fail(NMX_ERR_INVALID, "step_wide_model: funnel_noncentered needs n == dim");
-      return launch_wide_model(w, NmxWideFunnelNC{n}, ws, cfg->ldc, s);
-    default:
-      return nmx_fail(NMX_ERR_INVALID, "step_wide_model: unknown model %d", model);
-  }
+  const WideArgs w{step_args(cfg, arena, samples, fields, transform), ns, slice_width(cfg->dim)};
+  return with_wide_model("step_wide_model", cfg, model, data, n, false, [&](const auto& m) {
+    return launch_wide_model(w, m, (char*)workspace, cfg->ldc, (hipStream_t)stream);
+  });
 }
 
 namespace {
-// threads per chain of the persistent wide kernel, from dim only (the sums' order depends on
-// it).  The NMX_PERSIST_NT environment override for kernel experiments exists only in the debug
-// build and in experiment builds (-DNMX_EXPERIMENT, scripts/ab_build.py): the release library's
-// results never depend on the environment.
-int persist_nt(int dim) {
-#if defined(NMX_DEBUG) || defined(NMX_EXPERIMENT)
-  if (const char* e = getenv("NMX_PERSIST_NT")) {
-    const int v = atoi(e);
-    if (v == 128 || v == 256 || v == 512 || v == 1024) return v;
-  }
-#endif
-  // SV (D = 2519): 256 -> 13.1M leapfrog/s at 8192 chains, 512 -> 9.6M; funnel-10k: 512 -> 5.1M,
-  // 256 -> 4.7M (profiles/r03/ab_persistent_nt.txt)
-  return dim <= 4096 ? 256 : 512;
-}
-
 // Whether the persistent kernel keeps the chain's frontier and inverse mass in LDS
 // (k_wide_persistent CARRY): its 16 D bytes beside the static LDS must fit the share of a CU's
 // 160 KB that the compiled occupancy (NMX_PX_OCC waves per SIMD, NT / 64 waves per workgroup)
@@ -3374,13 +3305,9 @@ int launch_persistent_nt(const StepArgs& args, const M& m, int max_steps, hipStr
 
 template <class M>
 int launch_persistent(const StepArgs& args, const M& m, int max_steps, hipStream_t s) {
-  int st;
-  switch (persist_nt(args.cfg.dim)) {
-    case 128: st = launch_persistent_nt<128>(args, m, max_steps, s); break;
-    case 256: st = launch_persistent_nt<256>(args, m, max_steps, s); break;
-    case 512: st = launch_persistent_nt<512>(args, m, max_steps, s); break;
-    default: st = launch_persistent_nt<1024>(args, m, max_steps, s);
-  }
+  const int st = with_persist_nt(persist_nt(args.cfg.dim), [&](auto nt) {
+    return launch_persistent_nt<decltype(nt)::value>(args, m, max_steps, s);
+  });
   if (st != NMX_OK) return st;
   return nmx_check_launch("k_wide_persistent");
 }
@@ -3418,34 +3345,12 @@ extern "C" int nmx_nuts_run_wide(const nmx_nuts_config* cfg, void* arena, float*
   if (group_count(*cfg) > 1) return nmx_fail(NMX_ERR_INVALID, "run_wide: one chain group only");
   if (cfg->sync_chains)
     return nmx_fail(NMX_ERR_INVALID, "run_wide: per-chain async only (lockstep: one launch per transition)");
-  // samples may be NULL: the per-transition fields alone are collected
-  if (cfg->collection_size > 0 && (!fields || !transform))
-    return nmx_fail(NMX_ERR_INVALID, "collection buffers are NULL");
+  if ((st = need_collection(cfg, fields, transform))) return st;
   if (max_steps <= 0) return nmx_fail(NMX_ERR_INVALID, "run_wide: max_steps must be positive");
-  // 32-bit byte offsets within a field
-  if ((size_t)cfg->ldc * cfg->dim * 4 > 0xFFFFFFF0ull)
-    return nmx_fail(NMX_ERR_INVALID, "run_wide: a vector field exceeds 4 GiB");
-  StepArgs args;
-  args.a = arena_of(cfg, arena);
-  args.cfg = *cfg;
-  args.samples = samples;
-  args.fields = fields;
-  args.transform = transform;
-  hipStream_t s = (hipStream_t)stream;
-  switch (model) {
-    case NMX_WIDE_STOCHASTIC_VOLATILITY:
-      if (!data || n <= 1 || n + 2 != cfg->dim)
-        return nmx_fail(NMX_ERR_INVALID, "run_wide: stochastic volatility needs returns[T], dim == T + 2");
-      return launch_persistent(args, NmxWideSV{data, n}, max_steps, s);
-    case NMX_WIDE_FUNNEL:
-      if (n != cfg->dim || n < 2) return nmx_fail(NMX_ERR_INVALID, "run_wide: funnel needs n == dim >= 2");
-      return launch_persistent(args, NmxWideFunnel{n}, max_steps, s);
-    case NMX_WIDE_FUNNEL_NONCENTERED:
-      if (n != cfg->dim || n < 2)
-        return nmx_fail(NMX_ERR_INVALID, "run_wide: funnel_noncentered needs n == dim >= 2");
-      return launch_persistent(args, NmxWideFunnelNC{n}, max_steps, s);
-    default:
-      return nmx_fail(NMX_ERR_INVALID, "run_wide: unknown model %d", model);
-  }
+  if ((st = need_field_below_4g(cfg, "run_wide"))) return st;
+  const StepArgs args = step_args(cfg, arena, samples, fields, transform);
+  return with_wide_model("run_wide", cfg, model, data, n, true, [&](const auto& m) {
+    return launch_persistent(args, m, max_steps, (hipStream_t)stream);
+  });
 }
 

@@ -103,14 +103,6 @@ __device__ __forceinline__ f32x16 x3_mma(const bf16x8& a, const bf16x8& b, f32x1
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
 }
 
-// VALU instructions the scheduling hints place after each GEMM1(k+1) / GEMM2(k) MFMA (x3_item)
-#ifndef NMX_X3_VALU1
-#define NMX_X3_VALU1 5
-#endif
-#ifndef NMX_X3_VALU2
-#define NMX_X3_VALU2 3
-#endif
-
 constexpr int X3_ROWS = 32;
 constexpr int X3_MAX_S = 256;
 
@@ -244,7 +236,7 @@ __device__ __forceinline__ void x3_wait_vm() {
 
 // A-piece (plane p, k-block kb) and combined-piece (c) positions in an LDS ring slot: the tile
 // image in HBM order, or (COMPACT, the main kernel with H = 1) the slot without the last
-// k-block's plane pieces, which only the transposed GEMM2 reads of the TR / tail forms need
+// k-block's plane pieces, which only the transposed GEMM2 reads of the tail form need
 template <int KB, bool COMPACT>
 __device__ constexpr int x3_ai(int p, int kb) { return COMPACT ? p * (KB - 1) + kb : p * KB + kb; }
 template <int KB, bool COMPACT>
@@ -501,49 +493,6 @@ __device__ __forceinline__ void x3_tr_wait(bf16x8 (&fb)[3][DT][2]) {
 #pragma unroll
       for (int sidx = 0; sidx < 2; ++sidx) asm volatile("" : "+v"(fb[plane][dt][sidx]));
 }
-// x3_gemm2 with the operands read just in time (three fragments per (s, dt), 12 VGPRs instead
-// of 48 held across GEMM1: the main kernel's register budget)
-template <int KB, int DT>
-__device__ __forceinline__ void x3_gemm2_tr(const char* aslot, const float (&res)[16], f32x16 (&g)[DT]) {
-  static_assert(KB >= 2 * DT, "the GEMM1 image must cover GEMM2's 32 DT columns");
-  const int L = threadIdx.x & 63;
-  const int p = L & 3, q = (L >> 2) & 3, g1 = (L >> 4) & 1, h = L >> 5;
-  const unsigned base = (unsigned)(size_t)((__attribute__((address_space(3))) const char*)aslot) + g1 * 1024 +
-                        (q + 32 * (p >> 1) + 4 * h) * 16 + 8 * (p & 1);
-#pragma unroll
-  for (int sidx = 0; sidx < 2; ++sidx) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = res[8 * sidx + j];
-    bf16x8 r1, r2, r3;
-    split3(v, r1, r2, r3);
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) {
-      typedef short s4 __attribute__((ext_vector_type(4)));
-      s4 t[6];
-      asm volatile(
-          "ds_read_b64_tr_b16 %0, %6 offset:%7\n\tds_read_b64_tr_b16 %1, %6 offset:%8\n\t"
-          "ds_read_b64_tr_b16 %2, %6 offset:%9\n\tds_read_b64_tr_b16 %3, %6 offset:%10\n\t"
-          "ds_read_b64_tr_b16 %4, %6 offset:%11\n\tds_read_b64_tr_b16 %5, %6 offset:%12\n\t"
-          "s_waitcnt lgkmcnt(0)"
-          : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3]), "=&v"(t[4]), "=&v"(t[5])
-          : "v"(base), "i"((0 * KB + 2 * dt) * 1024 + 16 * sidx * 16), "i"((0 * KB + 2 * dt) * 1024 + (16 * sidx + 8) * 16),
-            "i"((1 * KB + 2 * dt) * 1024 + 16 * sidx * 16), "i"((1 * KB + 2 * dt) * 1024 + (16 * sidx + 8) * 16),
-            "i"((2 * KB + 2 * dt) * 1024 + 16 * sidx * 16), "i"((2 * KB + 2 * dt) * 1024 + (16 * sidx + 8) * 16));
-      bf16x8 b1, b2, b3;
-      __builtin_memcpy(&b1, &t[0], 16);
-      __builtin_memcpy(&b2, &t[2], 16);
-      __builtin_memcpy(&b3, &t[4], 16);
-      g[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b3, r1, g[dt], 0, 0, 0);
-      g[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b2, r2, g[dt], 0, 0, 0);
-      g[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, r3, g[dt], 0, 0, 0);
-      g[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b2, r1, g[dt], 0, 0, 0);
-      g[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, r2, g[dt], 0, 0, 0);
-      g[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, r1, g[dt], 0, 0, 0);
-    }
-  }
-}
-
 // x3_gemm2 on register operands (same products in the same order)
 template <int DT>
 __device__ __forceinline__ void x3_gemm2_regs(const bf16x8 (&fb)[3][DT][2], const float (&res)[16],
@@ -570,21 +519,15 @@ __device__ __forceinline__ void x3_gemm2_regs(const bf16x8 (&fb)[3][DT][2], cons
 
 // Software-pipelined: GEMM1 of tile k+1 is issued beside the epilogue of tile k (they are
 // independent), then GEMM2 of tile k.  SCHED 0 adds the igrouplp placement hints below.
-//
-#ifndef NMX_X3_TR
-#define NMX_X3_TR 0
-#endif
-// the main kernel's GEMM2 operand from transposed reads of the GEMM1 image (needs KB >= 2 DT)
-template <int KB, int DT>
-constexpr bool x3_tr() { return NMX_X3_TR && KB >= 2 * DT; }
+
 // A pieces of a main-kernel LDS A slot: without the last k-block's plane pieces when the
-// combined pieces replace them (H) and GEMM2 does not read the slot (not TR)
-template <int KB, int DT, int H>
-constexpr int x3_nal() { return (H && !x3_tr<KB, DT>()) ? 3 * (KB - 1) + 2 : 3 * KB + 2 * H; }
+// combined pieces replace them (H; GEMM2 reads the B ring, not the slot)
+template <int KB, int H>
+constexpr int x3_nal() { return H ? 3 * (KB - 1) + 2 : 3 * KB; }
 template <int KB, int DT, int H>
 inline size_t x3_lds_bytes() {
   constexpr int NA = 3 * KB + 2 * H, NP = NA + 6 * DT + 1;
-  return x3_tr<KB, DT>() ? (size_t)(3 * NA + 2) * 1024 : (size_t)2 * (x3_nal<KB, DT, H>() + NP - NA) * 1024;
+  return (size_t)2 * (x3_nal<KB, H>() + NP - NA) * 1024;
 }
 
 
@@ -629,6 +572,14 @@ inline size_t x3_lds_bytes() {
 // an operand fragment is read this many MFMAs ahead of its first use
 #ifndef NMX_X3_LEAD
 #define NMX_X3_LEAD 2
+#endif
+// SCHED 0: VALU instructions the scheduling hints place after each GEMM1(k+1) / GEMM2(k) MFMA
+// (x3_item; the measurement is at the hints)
+#ifndef NMX_X3_VALU1
+#define NMX_X3_VALU1 5
+#endif
+#ifndef NMX_X3_VALU2
+#define NMX_X3_VALU2 3
 #endif
 
 // the lane's index in its wave from the execution mask, behind an empty asm the compiler cannot
@@ -758,17 +709,13 @@ __device__ __forceinline__ void x3_item(const char* __restrict__ Xq, int64_t nti
     // Split rings: GEMM1 reads only the A part of a tile (pieces < 3 KB), GEMM2 and the labels
     // only the B part.  Iteration k reads A(k+1) and B(k) while A(k+2) and B(k+1) fill, so two
     // slots of each part suffice: 2 x (12 + 13) KB for covtype, three workgroups per CU.
-    // TR (x3_tr<KB, DT>()): GEMM2 reads X^T from the GEMM1 image by transposed LDS reads, so
-    // only the A pieces and the labels are streamed (half the bytes); the A ring then keeps
-    // tile k for GEMM2(k) beside tile k+1 (GEMM1) and tile k+2 landing: 3 slots, and B slots
-    // hold the label piece only (3 x 12 + 2 x 1 KB)
-    // With H the A part also holds the two combined pieces; the non-TR slot skips the last
+    // With H the A part also holds the two combined pieces, and its slot skips the last
     // k-block's plane pieces (NAL = 11 of 14 for covtype, x3_ai / x3_ci COMPACT positions).
+    // A B slot is the tile's B part as packed, the label piece last.
     constexpr int NA = 3 * KB + 2 * H, NBP = NP - NA;
-    constexpr bool TR = x3_tr<KB, DT>();
-    constexpr int NAL = x3_nal<KB, DT, H>();
+    constexpr int NAL = x3_nal<KB, H>();
     constexpr bool CMP = NAL != NA;
-    constexpr int ASL = TR ? 3 : 2, BSZ = TR ? 1 : NBP;
+    constexpr int ASL = 2, BSZ = NBP;  // A slots; pieces of a B slot
     char* aring = lds;
     char* bring = lds + ASL * NAL * 1024;
     auto issue_a = [&](int k) {
@@ -785,18 +732,12 @@ __device__ __forceinline__ void x3_item(const char* __restrict__ Xq, int64_t nti
     };
     auto issue_b = [&](int k) {
       char* dst = bring + (k & 1) * BSZ * 1024;
-      if constexpr (TR) {
-        if (wu == 3)
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)dst, 16, lane * 16,
-                                                   (unsigned)((k * NP + NP - 1) * 1024), 0, 0);
-      } else {
 #pragma unroll
-        for (int j = 0; j < (NBP + 3) / 4; ++j) {
-          const int i = wu + 4 * j;
-          if (i < NBP)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)(dst + i * 1024),
-                                                     16, lane * 16, (unsigned)((k * NP + NA + i) * 1024), 0, 0);
-        }
+      for (int j = 0; j < (NBP + 3) / 4; ++j) {
+        const int i = wu + 4 * j;
+        if (i < NBP)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)(dst + i * 1024), 16,
+                                                   lane * 16, (unsigned)((k * NP + NA + i) * 1024), 0, 0);
       }
     };
     if (nt > 0) {
@@ -808,7 +749,6 @@ __device__ __forceinline__ void x3_item(const char* __restrict__ Xq, int64_t nti
       f32x16 accA, accB;
       if (active) accA = x3_gemm1<KB, H, CMP>(reinterpret_cast<const bf16x8*>(aring) + lane, z1, z2, z3);
       if constexpr (SCHED == 1) {
-        static_assert(!TR, "SCHED 1 reads GEMM2's operand from the B ring");
         constexpr int ROT = NMX_X3_ROT, LEAD = NMX_X3_LEAD;
         constexpr int NM1 = 6 * (KB - H) + 3 * H, NM2 = 12 * DT;  // MFMAs of GEMM1, GEMM2
         static_assert(ROT >= 0 && ROT <= 16 && LEAD >= 1 && LEAD <= NM1 && NM1 <= x3s::MAXG && NM2 <= x3s::MAXG, "plan");
@@ -1005,8 +945,7 @@ __device__ __forceinline__ void x3_item(const char* __restrict__ Xq, int64_t nti
         float res[16];
         nxt = x3_gemm1<KB, H, CMP>(fa, z1, z2, z3);
         x3_epilogue(acc, y4, res, pe);
-        if constexpr (TR) x3_gemm2_tr<KB, DT>(aring + (k % ASL) * NAL * 1024, res, g);
-        else x3_gemm2<NA, DT>(reinterpret_cast<const bf16x8*>(bs) - NA * 64 + lane, res, g);
+        x3_gemm2<NA, DT>(reinterpret_cast<const bf16x8*>(bs) - NA * 64 + lane, res, g);
         if constexpr (SCHED == 0) {
           // scheduling hints (LLVM igrouplp): each GEMM1(k+1) MFMA followed by 5 VALU (tile k's
           // epilogue and the first split half), each GEMM2(k) MFMA by 3 (the second split half),
