@@ -768,6 +768,71 @@ size_t nmx_psis_workspace_bytes(int num_rows, int num_columns);
 int nmx_psis_loo(const float* table, int num_rows, int64_t ld, int num_columns, int tail, void* workspace,
                  float* elpd_loo, float* pareto_k, void* stream);
 
+/* ---- stochastic variational inference (numpyro/infer/svi.py SVI.update, numpyro/infer/elbo.py
+ *      Trace_ELBO, numpyro/infer/autoguide.py AutoNormal / AutoDiagonalNormal, numpyro/optim.py
+ *      Adam / SGD): a mean-field normal guide q(z) = N(loc, diag(scale^2)) over the unconstrained
+ *      coordinates z[D], scale = softplus(rho), fitted by reparameterised gradient steps on
+ *        loss = mean_p U(z_p) - sum_d log scale_d - D / 2 (1 + log 2 pi),   z_p = loc + scale eps_p,
+ *      the negative ELBO with the guide's entropy in closed form.  A particle is one position of
+ *      a potential launch (nmx_eval_batch with num_chains = P, no phase, no list), so a step is
+ *      that launch plus nmx_svi_step.
+ *
+ * Draws: eps of particle p, coordinate d, iteration word t and event e is normal number d % 4 of
+ * the block nmx_rng(seed, p, t, e, d / 4, 0): Box-Muller cos and sin of the words (x, y), then of
+ * (z, w), as the momentum draw orders them.  e = NMX_EV_SVI = 9 with t = the step for the ELBO
+ * particles, e = NMX_EV_GUIDE = 10 with t = 0 and p = the sample index for draws from a fitted
+ * guide.  z = loc + scale * eps in f32 with both roundings.
+ *
+ * Parameters: par is [NMX_SVI_ROWS][dim] f32, the rows of enum nmx_svi_row; a step reads the copy
+ * of step t and writes the copy of step t + 1 (two buffers, swapped by the caller), so no
+ * workgroup reads a value another workgroup of the launch has written.
+ *
+ * nmx_svi_step is ONE launch of ceil(dim / 4) + 1 workgroups of 1024 threads.  Workgroup b owns the
+ * coordinates 4 b .. 4 b + 3, wave q of it the row d = 4 b + q of grad, eps and z ([dim][ldc],
+ * particles contiguous; the other waves only draw):
+ *   g_loc[d]   = (sum_p grad[d][p]) / P
+ *   g_scale[d] = (sum_p grad[d][p] * eps[d][p]) / P - 1 / scale[d]
+ *   g_rho[d]   = g_scale[d] * sigmoid(rho[d])
+ * each sum with lane l adding p = l, l + 64, ... in order and the xor butterfly (32, 16, ..., 1)
+ * over the lanes: an order fixed by P alone, no atomics.  Then the optimiser, for x in (loc, rho):
+ *   NMX_SVI_SGD:  x -= step_size * g
+ *   NMX_SVI_ADAM: m = (1 - b1) g + b1 m, v = (1 - b2) g^2 + b2 v,
+ *                 x -= step_size * (m / c1) / (sqrt(v / c2) + eps), c_i = 1 - b_i^(t + 1)
+ *                 (jax.example_libraries.optimizers.adam; c_i is formed in f64 on the host)
+ * scale = softplus(rho) = max(rho, 0) + log1p(exp(-|rho|)), and the workgroup writes its four rows
+ * of eps and z for step t + 1 from the new loc and scale.  The last workgroup writes
+ *   *loss = (sum_p pe[p]) / P - sum_d log(scale[d]) - dim / 2 (1 + log 2 pi)
+ * from the scale of step t, both sums in the lane order above.  Pad particles P .. ldc - 1 are
+ * neither read nor written; nor is a coordinate >= dim of the last block.
+ * ---- */
+enum nmx_svi_optimizer { NMX_SVI_SGD = 0, NMX_SVI_ADAM = 1 };
+enum nmx_svi_row {
+  NMX_SVI_LOC = 0, NMX_SVI_RHO, NMX_SVI_SCALE, /* scale = softplus(rho), kept beside rho */
+  NMX_SVI_M_LOC, NMX_SVI_V_LOC, NMX_SVI_M_RHO, NMX_SVI_V_RHO, /* Adam moments (unused by SGD) */
+  NMX_SVI_ROWS
+};
+#define NMX_SVI_EVENT_STEP 9   /* NMX_EV_SVI */
+#define NMX_SVI_EVENT_GUIDE 10 /* NMX_EV_GUIDE */
+typedef struct nmx_svi_config {
+  int32_t dim;           /* D */
+  int32_t num_particles; /* P */
+  int32_t ldc;           /* leading dimension of z / eps / grad: >= P, a multiple of 64 */
+  int32_t optimizer;     /* nmx_svi_optimizer */
+  float step_size, b1, b2, eps;
+  uint64_t seed;         /* Philox key */
+} nmx_svi_config;
+/* Draw-only mode: z[d][p] = loc[d] + scale[d] * eps[d][p] for p < num_particles, d < dim, eps the
+ * normals of (seed, particle_offset + p, iter, event); eps_out ([dim][ldc], may be NULL) keeps
+ * them.  event is NMX_SVI_EVENT_STEP or NMX_SVI_EVENT_GUIDE.  cfg's optimiser fields are unused. */
+int nmx_svi_draw(const nmx_svi_config* cfg, const float* loc, const float* scale, int event, uint32_t iter,
+                 int64_t particle_offset, float* z, float* eps_out, void* stream);
+/* One optimisation step t >= 0 (above): reads par_cur, grad, pe and eps of step t; writes par_next,
+ * loss[0], and z and eps of step t + 1.  par_cur and par_next must not overlap. */
+int nmx_svi_step(const nmx_svi_config* cfg, int step, const float* par_cur, float* par_next, const float* grad,
+                 const float* pe, float* z, float* eps, float* loss, void* stream);
+/* The loss of nmx_svi_step alone (one workgroup): loss[0] from pe and the scale row of par. */
+int nmx_svi_loss(const nmx_svi_config* cfg, const float* par, const float* pe, float* loss, void* stream);
+
 /* ---- self tests (no reference counterpart; used by tests and smoke()) ---- */
 /* Philox4x32-10 on device: ctr_key is n x {c0,c1,c2,c3,k0,k1}, out is n x 4 words. */
 int nmx_selftest_philox(const uint32_t* ctr_key, uint32_t* out, int n, void* stream);

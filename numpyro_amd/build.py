@@ -47,7 +47,8 @@ COMMON_FLAGS = [
 #   program potential and predictive program (bodies in a header, nmx_program.h, like the small
 #   models; the predictive draws' accept tests round like their NumPy restatement, and so do the
 #   log-likelihood program and the Welford / Chan merges of its pointwise reductions, and the
-#   PSIS kernel's log ratios and sums): the
+#   PSIS kernel's log ratios and sums, and the SVI step's z = loc + scale * eps, gradient sums and
+#   optimiser): the
 #   same device function is inlined into several kernels (the launched step, the persistent
 #   schedule, the sync / async schedules), and whether the backend fuses a * b + c into an FMA
 #   depends on each kernel's code generation -- with contraction off every kernel rounds every
@@ -58,7 +59,8 @@ FILE_FLAGS = {"potential_logreg.hip": ["-fno-slp-vectorize"],
               "potential_program.hip": ["-ffp-contract=off"],
               "predictive_program.hip": ["-ffp-contract=off"],
               "loglik_program.hip": ["-ffp-contract=off"],
-              "psis.hip": ["-ffp-contract=off"]}
+              "psis.hip": ["-ffp-contract=off"],
+              "svi.hip": ["-ffp-contract=off"]}
 
 
 def _headers():

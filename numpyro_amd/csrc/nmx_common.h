@@ -41,6 +41,8 @@ enum nmx_rng_event : uint32_t {
   NMX_EV_ACCEPT = 6u,     // HMC Metropolis accept
   NMX_EV_PREDICT = 7u,    // predictive draw: iter word = site / stream id, word2 = element, word3 = attempt
   NMX_EV_HEURISTIC = 8u,  // find_reasonable_step_size momentum, word2 = block, word3 = attempt
+  NMX_EV_SVI = 9u,        // ELBO particle noise: chain word = particle, iter word = step, word2 = block
+  NMX_EV_GUIDE = 10u,     // draw from a fitted guide: chain word = sample, iter word = 0, word2 = block
 };
 
 struct nmx_u4 { uint32_t x, y, z, w; };

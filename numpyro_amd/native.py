@@ -151,7 +151,23 @@ class Program(ctypes.Structure):
                 ("num_index", ctypes.c_int32), ("dim", ctypes.c_int32)]
 
 
+SVI_SGD, SVI_ADAM = 0, 1  # enum nmx_svi_optimizer
+# enum nmx_svi_row: the rows of the SVI parameter buffer [SVI_ROWS][D]
+SVI_ROW_NAMES = ["loc", "rho", "scale", "m_loc", "v_loc", "m_rho", "v_rho"]
+SVI_ROWS = len(SVI_ROW_NAMES)  # NMX_SVI_ROWS
+SVI_EVENT_STEP, SVI_EVENT_GUIDE = 9, 10  # NMX_SVI_EVENT_STEP (NMX_EV_SVI), NMX_SVI_EVENT_GUIDE (NMX_EV_GUIDE)
+
+
+class SviConfig(ctypes.Structure):
+    """Mirror of nmx_svi_config."""
+
+    _fields_ = [("dim", ctypes.c_int32), ("num_particles", ctypes.c_int32), ("ldc", ctypes.c_int32),
+                ("optimizer", ctypes.c_int32), ("step_size", ctypes.c_float), ("b1", ctypes.c_float),
+                ("b2", ctypes.c_float), ("eps", ctypes.c_float), ("seed", ctypes.c_uint64)]
+
+
 _P = ctypes.POINTER
+_svip = _P(SviConfig)
 _cfgp = _P(NutsConfig)
 _evp = _P(EvalBatch)
 _progp = _P(Program)
@@ -208,6 +224,9 @@ SIGNATURES: dict[str, tuple] = {
     "nmx_pointwise_finish": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp]),
     "nmx_psis_workspace_bytes": (c_size, [c_int, c_int]),
     "nmx_psis_loo": (c_int, [c_vp, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "nmx_svi_draw": (c_int, [_svip, c_vp, c_vp, c_int, ctypes.c_uint32, c_i64, c_vp, c_vp, c_vp]),
+    "nmx_svi_step": (c_int, [_svip, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "nmx_svi_loss": (c_int, [_svip, c_vp, c_vp, c_vp, c_vp]),
     "nmx_logreg_packed_bytes": (c_size, [c_i64, c_int]),
     "nmx_logreg_pack": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     "nmx_logreg_workspace_bytes": (c_size, [c_i64, c_int, c_int]),

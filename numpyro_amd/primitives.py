@@ -38,7 +38,8 @@ def deterministic(name, value):
 
 
 def param(name, init_value=None, **kwargs):
-    raise NotImplementedError("numpyro.param belongs to SVI, outside this engine")
+    raise NotImplementedError(f"numpyro.param({name!r}): `param` sites in models and hand-written guides are not "
+                              "supported; SVI optimises the parameters of an autoguide (infer.autoguide.AutoNormal)")
 
 
 @contextlib.contextmanager
