@@ -397,6 +397,21 @@ size_t nmx_pe_bnn_workspace_bytes(int Dx, int H, int num_chains);
  *     (~ref), at least one a slot.  Adjoint: w = L^-T g_dst by back substitution, g_b += w,
  *     g_a[i][j] -= w[i] dst[j] for j <= i, each only where the operand is a slot.
  *     1 <= n <= NMX_CHOL_MAX_N.
+ *   NMX_OP_LRISING (elementwise, binary): dst[i] = lgamma(a + k) - lgamma(a) - k log(a), the log
+ *     rising factorial of a > 0 over k >= 0 steps less its large-a limit k log(a), so that it
+ *     tends to 0 as a -> inf (k (k - 1) / (2 a) there).  a is a slot or a constant, k = b must be
+ *     a constant (data): the check refuses a slot.  No lgamma or digamma difference is formed:
+ *     whole k <= NMX_LRISING_SUM_MAX is sum_{0 < j < k} log1p(j / a); otherwise a is shifted up
+ *     by the recurrence to x = a + m >= 8 (m <= 8 steps) and the Stirling difference is taken as
+ *     x (log1p(t) - t) + (k - 1/2) log1p(t) + s(x + k) - s(x), t = k / x, s the Stirling tail
+ *     1/(12 x) - 1/(360 x^3) + 1/(1260 x^5) - 1/(1680 x^7), log1p(t) - t by its own series below t = 1/2; the
+ *     shift adds k log1p(m / a) - sum_{j < m} log1p(k / (a + j)).  Adjoint:
+ *     g_a += g_dst (digamma(a + k) - digamma(a) - k / a), as -sum_{0 < j < k} j / (a (a + j)) or
+ *     the derivative of the Stirling form term by term.  NaN unless a > 0 and k >= 0.
+ *   NMX_OP_LOGADDEXP (elementwise, binary): dst[i] = log(exp(a) + exp(b)) =
+ *     max(a, b) + log1p(exp(-|a - b|)), the gap taken as 0 where a == b (two -inf give -inf).
+ *     Adjoint: the two softmax weights, g_a += g_dst exp(a - dst), g_b += g_dst exp(b - dst),
+ *     both 0 where dst is -inf.  Operand forms as NMX_OP_ADD.
  * Sums run in an order fixed by the program alone (per-lane strided partial sums, then a
  * fixed butterfly over the 64 lanes), with no atomics: U and the gradient are bitwise
  * independent of chain count, position, ldc, list order. ---- */
@@ -415,6 +430,13 @@ enum nmx_linalg_opcode {
   NMX_OP_CHOLESKY = 32, NMX_OP_TRISOLVE,
   NMX_LINALG_END
 };
+/* The special-function ops: elementwise binary ops (operand forms, lanes and barriers of
+ * NMX_OP_ADD ... NMX_OP_POW), numbered apart from nmx_opcode like the dense ops. */
+enum nmx_special_opcode {
+  NMX_OP_LRISING = 40, NMX_OP_LOGADDEXP,
+  NMX_SPECIAL_END
+};
+#define NMX_LRISING_SUM_MAX 8
 #define NMX_CHOL_MAX_N 128
 #define NMX_OP_WORDS 8
 

@@ -42,6 +42,74 @@ __device__ __forceinline__ float nmx_digammaf(float x) {
   return logf(x) - 0.5f * r - tail - shift;
 }
 
+// ---- NMX_OP_LRISING (include/numpyro_amd.h): R(a, k) = lgamma(a + k) - lgamma(a) - k log(a) and
+// dR/da = digamma(a + k) - digamma(a) - k / a, neither as a difference of two lgamma / digamma
+// values.  program.py _host_lrising restates both in float64 and float32.
+//
+// log1p(t) - t, t >= 0: below 1/2 the series of 2 atanh(s) - t at s = t / (2 + t), whose first
+// term 2 s - t is -s t exactly (s^2 <= 0.04: the term after s^16 / 17 is below 1e-12 of the sum, so
+// the float64 restatement of the host interpreter runs the same series)
+__device__ __forceinline__ float nmx_log1pmx(float t) {
+  if (!(t < 0.5f)) return log1pf(t) - t;
+  const float s = t / (2.0f + t), s2 = s * s;
+  float odd = 1.0f / 15 + s2 * (1.0f / 17);
+  odd = 1.0f / 9 + s2 * (1.0f / 11 + s2 * (1.0f / 13 + s2 * odd));
+  odd = 1.0f / 3 + s2 * (1.0f / 5 + s2 * (1.0f / 7 + s2 * odd));
+  return s * (2.0f * s2 * odd - t);
+}
+
+// the Stirling tail lgamma(x) - ((x - 1/2) log x - x + log(2 pi) / 2) and its derivative, x >= 8
+// (the next terms, 1 / (1188 x^9) and 1 / (132 x^10), are below 1e-11 there: the float64 restatement
+// of the host interpreter runs the same series)
+__device__ __forceinline__ float nmx_stirling_s(float x) {
+  const float r = 1.0f / x, r2 = r * r;
+  return (1.0f / 12 - (1.0f / 360 - (1.0f / 1260 - (1.0f / 1680) * r2) * r2) * r2) * r;
+}
+__device__ __forceinline__ float nmx_stirling_ds(float x) {
+  const float r = 1.0f / x, r2 = r * r;
+  return -r2 * (1.0f / 12 - r2 * (1.0f / 120 - r2 * (1.0f / 252 - r2 * (1.0f / 240))));
+}
+
+__device__ __forceinline__ bool nmx_lrising_by_sum(float k) { return k <= (float)NMX_LRISING_SUM_MAX && k == floorf(k); }
+
+__device__ __forceinline__ float nmx_lrising(float a, float k) {
+  if (!(a > 0.0f) || !(k >= 0.0f)) return NAN;
+  if (nmx_lrising_by_sum(k)) {
+    float s = 0.0f;
+    for (int j = 1; j < NMX_LRISING_SUM_MAX; ++j)
+      if ((float)j < k) s += log1pf((float)j / a);
+    return s;
+  }
+  float x = a, shift = 0.0f, m = 0.0f;
+  for (int j = 0; j < 8 && x < 8.0f; ++j) {
+    shift += log1pf(k / x);
+    x += 1.0f;
+    m += 1.0f;
+  }
+  const float t = k / x;
+  const float body = x * nmx_log1pmx(t) + (k - 0.5f) * log1pf(t) + (nmx_stirling_s(x + k) - nmx_stirling_s(x));
+  return body + (k * log1pf(m / a) - shift);
+}
+
+__device__ __forceinline__ float nmx_lrising_da(float a, float k) {
+  if (!(a > 0.0f) || !(k >= 0.0f)) return NAN;
+  if (nmx_lrising_by_sum(k)) {
+    float s = 0.0f;
+    for (int j = 1; j < NMX_LRISING_SUM_MAX; ++j)
+      if ((float)j < k) s += (float)j / (a * (a + (float)j));
+    return -s;
+  }
+  float x = a, shift = 0.0f, m = 0.0f;
+  for (int j = 0; j < 8 && x < 8.0f; ++j) {
+    shift += k / (x * (x + k));
+    x += 1.0f;
+    m += 1.0f;
+  }
+  const float body =
+      nmx_log1pmx(k / x) + 0.5f * k / (x * (x + k)) + (nmx_stirling_ds(x + k) - nmx_stirling_ds(x));
+  return body + (shift - k * m / (a * x));
+}
+
 struct NmxOp {
   int op, dst, a, b, n, sa, sb, aux;
 };
@@ -58,8 +126,11 @@ struct NmxProgram {
     NMX_DCHECK(ref >= 0 ? ref + i < p.num_slots : ~ref + i < p.num_consts);
     return ref >= 0 ? v[ref + i] : p.consts[~ref + i];
   }
+  // the special ops (nmx_special_opcode) are elementwise and binary, numbered after the ops that are neither
+  __device__ __forceinline__ static bool special(int op) { return op >= NMX_OP_LRISING && op < NMX_SPECIAL_END; }
+  __device__ __forceinline__ static bool elementwise(int op) { return op < NMX_OP_REDUCE_SUM || special(op); }
   // the ops that read values other lanes wrote
-  __device__ __forceinline__ static bool crosses(const NmxOp& o) { return o.op >= NMX_OP_REDUCE_SUM; }
+  __device__ __forceinline__ static bool crosses(const NmxOp& o) { return !elementwise(o.op); }
   __device__ __forceinline__ static bool wave_per_row(int rows, int cols) { return rows < 64 && cols >= 64; }
 
   __device__ __forceinline__ static float fwd(int op, float x, float y) {
@@ -77,6 +148,8 @@ struct NmxProgram {
       case NMX_OP_SUB: return x - y;
       case NMX_OP_MUL: return x * y;
       case NMX_OP_DIV: return x / y;
+      case NMX_OP_LRISING: return nmx_lrising(x, y);
+      case NMX_OP_LOGADDEXP: return fmaxf(x, y) + log1pf(expf(x == y ? 0.0f : -fabsf(x - y)));
       default: return powf(x, y);  // NMX_OP_POW
     }
   }
@@ -97,12 +170,17 @@ struct NmxProgram {
       case NMX_OP_SUB: da = gd; db = -gd; break;
       case NMX_OP_MUL: da = gd * y; db = gd * x; break;
       case NMX_OP_DIV: da = gd / y; db = -(gd * out) / y; break;
+      case NMX_OP_LRISING: da = gd * nmx_lrising_da(x, y); break;  // k is data: no adjoint
+      case NMX_OP_LOGADDEXP:
+        da = out == -INFINITY ? 0.0f : gd * expf(x - out);
+        db = out == -INFINITY ? 0.0f : gd * expf(y - out);
+        break;
       default: da = gd * (y * powf(x, y - 1.0f)); db = gd * (out * logf(x)); break;  // NMX_OP_POW
     }
   }
 
   __device__ __forceinline__ void forward(const NmxOp& o, float* v, int lane) const {
-    if (o.op < NMX_OP_REDUCE_SUM) {
+    if (elementwise(o.op)) {
       const bool binary = o.op >= NMX_OP_ADD;
       for (int i = lane; i < o.n; i += 64) {
         const float x = operand(v, o.a, i * o.sa);
@@ -189,7 +267,7 @@ struct NmxProgram {
   __device__ __forceinline__ static float lse_shift(float m) { return fabsf(m) < INFINITY ? m : 0.0f; }
 
   __device__ __forceinline__ void reverse(const NmxOp& o, const float* v, float* g, int lane) const {
-    if (o.op < NMX_OP_REDUCE_SUM) {
+    if (elementwise(o.op)) {
       const bool binary = o.op >= NMX_OP_ADD;
       const bool ga = o.a >= 0, gb = binary && o.b >= 0;
       float pa = 0.0f, pb = 0.0f;  // adjoint of a broadcast scalar: this lane's part
@@ -411,13 +489,13 @@ struct NmxProgram {
 
   // a broadcast scalar slot is read by every lane and was written by lane 0
   __device__ __forceinline__ static bool reads_scalar_slot(const NmxOp& o) {
-    if (o.op >= NMX_OP_REDUCE_SUM || o.n == 1) return false;
+    if (!elementwise(o.op) || o.n == 1) return false;
     return (o.a >= 0 && !o.sa) || (o.op >= NMX_OP_ADD && o.b >= 0 && !o.sb);
   }
   // z slots are referenced at any offset: their adjoints have no fixed lane
   __device__ __forceinline__ bool touches_z(const NmxOp& o) const {
     const bool b_is_operand =
-        (o.op >= NMX_OP_ADD && o.op < NMX_OP_REDUCE_SUM) || o.op == NMX_OP_CONCAT || o.op == NMX_OP_TRISOLVE;
+        (o.op >= NMX_OP_ADD && elementwise(o.op)) || o.op == NMX_OP_CONCAT || o.op == NMX_OP_TRISOLVE;
     return (o.a >= 0 && o.a < p.dim) || (b_is_operand && o.b >= 0 && o.b < p.dim);
   }
 

@@ -12,7 +12,11 @@
 
 namespace {
 
-__global__ __launch_bounds__(64) void k_program(NmxProgram prog, nmx_eval_batch ev) {
+// 7 waves / SIMD was the kernel's occupancy before the special ops (67 VGPRs); their cases made the
+// allocator take 75 (6 waves) although no path needs them all at once.  With the occupancy stated
+// it allocates 72, without a spill or scratch (as k_program_predict, predictive_program.hip).
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void k_program(NmxProgram prog,
+                                                                                        nmx_eval_batch ev) {
   const int pos = blockIdx.x;
   const int c = nmx_eval_chain(ev, pos);
   if (c < 0) return;
@@ -23,6 +27,7 @@ const char* const OP_NAMES[NMX_NUM_OPCODES] = {"neg", "exp", "log", "sqrt", "tan
                                                "lgamma", "add", "sub", "mul", "div", "pow", "reduce_sum",
                                                "gather", "matvec", "cumsum", "logsumexp", "concat"};
 const char* const LINALG_NAMES[NMX_LINALG_END - NMX_OP_CHOLESKY] = {"cholesky", "trisolve"};
+const char* const SPECIAL_NAMES[NMX_SPECIAL_END - NMX_OP_LRISING] = {"lrising", "logaddexp"};
 const char* const DRAW_NAMES[NMX_DRAW_END - NMX_DRAW_NORMAL] = {"draw_normal", "draw_exponential", "draw_cauchy",
                                                                 "draw_gamma", "draw_bernoulli", "draw_poisson",
                                                                 "draw_uniform", "draw_binomial"};
@@ -48,9 +53,13 @@ int nmx_program_check_impl(const nmx_program* hp, bool predictive, const int32_t
     const int op = w[0], dst = w[1], a = w[2], b = w[3], n = w[4], sa = w[5], sb = w[6], aux = w[7];
     const bool draw = predictive && op >= NMX_DRAW_NORMAL && op < NMX_DRAW_END;
     const bool linalg = op >= NMX_OP_CHOLESKY && op < NMX_LINALG_END;
-    if (!draw && !linalg && (op < 0 || op >= NMX_NUM_OPCODES))
+    const bool special = op >= NMX_OP_LRISING && op < NMX_SPECIAL_END;
+    if (!draw && !linalg && !special && (op < 0 || op >= NMX_NUM_OPCODES))
       return nmx_fail(NMX_ERR_INVALID, "op %d: bad opcode %d", k, op);
-    const char* nm = draw ? DRAW_NAMES[op - NMX_DRAW_NORMAL] : linalg ? LINALG_NAMES[op - NMX_OP_CHOLESKY] : OP_NAMES[op];
+    const char* nm = draw      ? DRAW_NAMES[op - NMX_DRAW_NORMAL]
+                     : linalg  ? LINALG_NAMES[op - NMX_OP_CHOLESKY]
+                     : special ? SPECIAL_NAMES[op - NMX_OP_LRISING]
+                               : OP_NAMES[op];
     if (n <= 0) return nmx_fail(NMX_ERR_INVALID, "op %d (%s): count %d <= 0", k, nm, n);
     const int64_t dst_len = op == NMX_OP_REDUCE_SUM ? 1 : n;
     if (dst != cursor || cursor + dst_len > p.num_slots)
@@ -108,7 +117,7 @@ int nmx_program_check_impl(const nmx_program* hp, bool predictive, const int32_t
       if (!predictive && a >= 0 && b >= 0 && a < p.dim && b < p.dim && a < b + lb && b < a + la)
         return nmx_fail(NMX_ERR_INVALID, "op %d (%s): operands z[%d:%lld] and z[%d:%lld] overlap", k, nm, a,
                         (long long)(a + la), b, (long long)(b + lb));
-    } else if (op < NMX_OP_REDUCE_SUM) {
+    } else if (op < NMX_OP_REDUCE_SUM || special) {
       const bool binary = op >= NMX_OP_ADD;
       if ((sa != 0 && sa != 1) || (sb != 0 && sb != 1))
         return nmx_fail(NMX_ERR_INVALID, "op %d (%s): strides %d, %d not 0 or 1", k, nm, sa, sb);
@@ -121,6 +130,9 @@ int nmx_program_check_impl(const nmx_program* hp, bool predictive, const int32_t
           return nmx_fail(NMX_ERR_INVALID, "op %d (%s): second operand %s %d (x%lld) out of range", k, nm,
                           b >= 0 ? "slot" : "constant", b >= 0 ? b : ~b, (long long)lb);
         if (a < 0 && b < 0) return nmx_fail(NMX_ERR_INVALID, "op %d (%s): both operands constant", k, nm);
+        if (op == NMX_OP_LRISING && b >= 0)
+          return nmx_fail(NMX_ERR_INVALID, "op %d (%s): the step count k is slot %d, it must be a constant (the op has "
+                          "no adjoint for it)", k, nm, b);
         // the adjoint of a z element has no fixed lane and the reverse op has no barrier between
         // its two updates: two z operands may share elements only as the same reference
         if (!predictive && a >= 0 && b >= 0 && a != b && a < p.dim && b < p.dim && a < b + lb && b < a + la)

@@ -11,7 +11,11 @@ Normal (continuous.py:2171), HalfCauchy (:700), Exponential (:455), Gamma (:490)
 (discrete.py:748; observed sites only), Uniform (continuous.py:2431), Beta (:165), Pareto (:2230),
 BinomialProbs / BinomialLogits / Binomial (discrete.py:172, :243, :298; observed sites only),
 Dirichlet (continuous.py), CategoricalProbs / CategoricalLogits / Categorical (discrete.py) and
-MixtureSameFamily (mixtures.py), the last two kinds as observed sites only; MultivariateNormal keeps a
+MixtureSameFamily (mixtures.py), the last two kinds as observed sites only; the count likelihoods
+GammaPoisson, NegativeBinomialProbs / NegativeBinomialLogits / NegativeBinomial, NegativeBinomial2,
+BetaBinomial (conjugate.py), GeometricProbs / GeometricLogits / Geometric, ZeroInflatedProbs /
+ZeroInflatedLogits / ZeroInflatedDistribution, ZeroInflatedPoisson (discrete.py) and
+ZeroInflatedNegativeBinomial2 (conjugate.py), observed sites only; MultivariateNormal keeps a
 symbolic covariance_matrix or scale_tril for the program compiler;
 ``.to_event`` / ``.expand`` (distribution.py:377-420).
 """
@@ -266,6 +270,169 @@ def Binomial(total_count=1, probs=None, logits=None):
     if (probs is None) == (logits is None):
         raise ValueError("One of `probs` or `logits` must be specified.")
     return BinomialLogits(logits, total_count) if logits is not None else BinomialProbs(probs, total_count)
+
+
+def _one_of(**kw):
+    if sum(v is not None for v in kw.values()) != 1:
+        raise ValueError("One of " + " or ".join(f"`{k}`" for k in kw) + " must be specified.")
+
+
+class GammaPoisson(Distribution):
+    """numpyro/distributions/conjugate.py:177 GammaPoisson: a Poisson whose rate is
+    Gamma(concentration, rate).  This and the count likelihoods below are observed sites only (a
+    discrete latent cannot be sampled by HMC); every parameter may depend on latent sites."""
+
+    support = "nonnegative_integer"
+
+    def __init__(self, concentration, rate=1.0):
+        super().__init__(_bshape(concentration, rate))
+        self.concentration, self.rate = concentration, rate
+
+    def params(self):
+        return {"concentration": self.concentration, "rate": self.rate}
+
+
+class NegativeBinomialProbs(Distribution):
+    """conjugate.py:240: GammaPoisson(total_count, 1 / probs - 1); probs is the chance that counts."""
+
+    support = "nonnegative_integer"
+
+    def __init__(self, total_count, probs):
+        super().__init__(_bshape(total_count, probs))
+        self.total_count, self.probs = total_count, probs
+
+    def params(self):
+        return {"total_count": self.total_count, "probs": self.probs}
+
+
+class NegativeBinomialLogits(Distribution):
+    """conjugate.py:254: GammaPoisson(total_count, exp(-logits))."""
+
+    support = "nonnegative_integer"
+
+    def __init__(self, total_count, logits):
+        super().__init__(_bshape(total_count, logits))
+        self.total_count, self.logits = total_count, logits
+
+    def params(self):
+        return {"total_count": self.total_count, "logits": self.logits}
+
+
+def NegativeBinomial(total_count, probs=None, logits=None):
+    """conjugate.py:231 dispatch on probs / logits."""
+    if probs is not None:
+        return NegativeBinomialProbs(total_count, probs)
+    if logits is not None:
+        return NegativeBinomialLogits(total_count, logits)
+    raise ValueError("One of `probs` or `logits` must be specified.")
+
+
+class NegativeBinomial2(Distribution):
+    """conjugate.py:276: GammaPoisson(concentration, concentration / mean)."""
+
+    support = "nonnegative_integer"
+
+    def __init__(self, mean, concentration):
+        super().__init__(_bshape(mean, concentration))
+        self.mean, self.concentration = mean, concentration
+
+    def params(self):
+        return {"mean": self.mean, "concentration": self.concentration}
+
+
+class BetaBinomial(Distribution):
+    """conjugate.py:26: a Binomial whose probability is Beta(concentration1, concentration0);
+    ``total_count`` is data, as Binomial's."""
+
+    support = "integer_interval"
+
+    def __init__(self, concentration1, concentration0, total_count=1):
+        super().__init__(_bshape(concentration1, concentration0, total_count))
+        self.concentration1, self.concentration0, self.total_count = concentration1, concentration0, total_count
+
+    def params(self):
+        return {"concentration1": self.concentration1, "concentration0": self.concentration0,
+                "total_count": self.total_count}
+
+
+class GeometricProbs(Distribution):
+    """discrete.py:868: failures before the first success, pmf (1 - probs)^k probs."""
+
+    support = "nonnegative_integer"
+
+    def __init__(self, probs):
+        super().__init__(_bshape(probs))
+        self.probs = probs
+
+    def params(self):
+        return {"probs": self.probs}
+
+
+class GeometricLogits(Distribution):
+    """discrete.py:909."""
+
+    support = "nonnegative_integer"
+
+    def __init__(self, logits):
+        super().__init__(_bshape(logits))
+        self.logits = logits
+
+    def params(self):
+        return {"logits": self.logits}
+
+
+def Geometric(probs=None, logits=None):
+    """discrete.py:951 dispatch on probs / logits."""
+    _one_of(probs=probs, logits=logits)
+    return GeometricProbs(probs) if probs is not None else GeometricLogits(logits)
+
+
+class ZeroInflatedProbs(Distribution):
+    """discrete.py:758: with probability ``gate`` a zero, else a draw of ``base_dist`` (a count
+    likelihood: Poisson, the negative binomial family, Geometric, Binomial or BetaBinomial)."""
+
+    def __init__(self, base_dist, gate):
+        if base_dist.event_shape:
+            raise ValueError(f"ZeroInflatedProbs expected empty base_dist.event_shape but got {base_dist.event_shape}")
+        super().__init__(tuple(np.broadcast_shapes(shape_of(gate), base_dist.batch_shape)))
+        self.base_dist, self.gate = base_dist, gate
+        self.support = base_dist.support
+
+    def params(self):
+        return {"base_dist": self.base_dist, "gate": self.gate}
+
+
+class ZeroInflatedLogits(Distribution):
+    """discrete.py:814: ZeroInflatedProbs with gate = sigmoid(gate_logits)."""
+
+    def __init__(self, base_dist, gate_logits):
+        if base_dist.event_shape:
+            raise ValueError(f"ZeroInflatedLogits expected empty base_dist.event_shape but got {base_dist.event_shape}")
+        super().__init__(tuple(np.broadcast_shapes(shape_of(gate_logits), base_dist.batch_shape)))
+        self.base_dist, self.gate_logits = base_dist, gate_logits
+        self.support = base_dist.support
+
+    def params(self):
+        return {"base_dist": self.base_dist, "gate_logits": self.gate_logits}
+
+
+def ZeroInflatedDistribution(base_dist, *, gate=None, gate_logits=None):
+    """discrete.py:832 dispatch on gate / gate_logits."""
+    _one_of(gate=gate, gate_logits=gate_logits)
+    return ZeroInflatedProbs(base_dist, gate) if gate is not None else ZeroInflatedLogits(base_dist, gate_logits)
+
+
+class ZeroInflatedPoisson(ZeroInflatedProbs):
+    """discrete.py:849 (the gate comes first, as there)."""
+
+    def __init__(self, gate, rate=1.0):
+        super().__init__(Poisson(rate), gate)
+        self.rate = rate
+
+
+def ZeroInflatedNegativeBinomial2(mean, concentration, *, gate=None, gate_logits=None):
+    """conjugate.py:293."""
+    return ZeroInflatedDistribution(NegativeBinomial2(mean, concentration), gate=gate, gate_logits=gate_logits)
 
 
 class Dirichlet(Distribution):

@@ -321,7 +321,7 @@ def potential_from_model(model, args=(), kwargs=None):
 _SYM_UNARY = {"tanh": "tanh", "exp": "exp", "sqrt": "sqrt", "log": "log", "neg": "neg", "log1p": "log1p",
               "square": "square", "expit": "sigmoid"}
 _SYM_OTHER = ("matmul", "sum", "getitem", "cumsum", "logsumexp", "concatenate")
-_SYM_BINARY = {"add": "add", "sub": "sub", "mul": "mul", "div": "div", "pow": "pow"}
+_SYM_BINARY = {"add": "add", "sub": "sub", "mul": "mul", "div": "div", "pow": "pow", "logaddexp": "logaddexp"}
 
 
 def eval_sym(x, values):

@@ -1,5 +1,5 @@
 """The array functions the reference's example models call on jax.numpy (matmul, dot, tanh,
-exp, log, log1p, sqrt, square, power, expit, sum, cumsum, logsumexp (jax.scipy.special's),
+exp, log, log1p, sqrt, square, power, logaddexp, expit, sum, cumsum, logsumexp (jax.scipy.special's),
 concatenate, zeros, ones, eye, shape, linalg.cholesky; indexing a vector), working on NumPy / torch
 arrays and on the symbolic values of latent sites (of rank <= 2 in elementwise expressions) while
 the model front end traces a model (numpyro_amd/frontend.py).  Write
@@ -166,6 +166,13 @@ def power(x, y):
     if isinstance(x, Sym) or isinstance(y, Sym):
         return Sym("pow", (x, y), np.broadcast_shapes(shape_of(x), shape_of(y)))
     return np.power(_np(x), _np(y))
+
+
+def logaddexp(x, y):
+    """jax.numpy.logaddexp: elementwise log(exp(x) + exp(y)) (the program's logaddexp op)."""
+    if isinstance(x, Sym) or isinstance(y, Sym):
+        return Sym("logaddexp", (x, y), np.broadcast_shapes(shape_of(x), shape_of(y)))
+    return np.logaddexp(_np(x), _np(y))
 
 
 def eye(n, dtype=None):

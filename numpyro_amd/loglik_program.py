@@ -5,7 +5,7 @@ The reference's ``log_likelihood`` re-runs the model once per posterior sample w
 sites substituted and reads ``site["fn"].log_prob(site["value"])`` of every observed site
 (numpyro/infer/util.py:1094-1170).  ``compile_log_likelihood`` traces the model once
 (frontend.trace_model) and lowers that run to a straight-line, draw-free program of the program
-compiler's format (numpyro_amd/program.py, the same builder and ``_LOGPROB`` expansions: folding,
+compiler's format (numpyro_amd/program.py, the same builder and ``_LOGPROB`` / ``_COUNT_LOGPROB`` expansions: folding,
 sharing and refusals are the same) whose inputs are the given sites' constrained values, as a
 predictive program's (predictive_program.py), and whose outputs are one value per observed site:
 its ``log_prob`` *before* any sum over the site, constants included.  One HIP kernel
@@ -23,8 +23,8 @@ import numpy as np
 
 from . import distributions as dist
 from .frontend import _base, _host
-from .program import (_BINOMIAL, _ELEMENTWISE, _LOGPROB, _ForwardProgram, _Refuse, _ew_mixture, _forward_prologue,
-                      _lp_mvn, _refuse)
+from .program import (_ELEMENTWISE, _ZERO_INFLATED, _ForwardProgram, _Refuse, _check_count_data, _ew_mixture,
+                      _forward_prologue, _logprob_entry, _lp_mvn, _lp_zero_inflated, _refuse)
 
 
 class LogLikOutput:
@@ -109,14 +109,13 @@ def compile_log_likelihood(model, args=(), kwargs=None, given=()):
         if s.obs is None:
             continue
         base = _base(s.fn)
-        expand, pnames, _ = _LOGPROB[type(base)]
+        expand, pnames, _ = _logprob_entry(base)
         xv = np.asarray(_host(s.obs), np.float64)
         shape = _batch_shape(s, base, xv.shape)
         n_site = int(np.prod(shape, dtype=np.int64))
         try:
             d = {p: lower.vector(getattr(base, p), s.name) for p in pnames}
-            if isinstance(base, _BINOMIAL) and not d["total_count"].is_const:
-                _refuse(s.name, "a total_count that depends on a latent site: it must be data")
+            _check_count_data(base, d, s.name)
             x = B.const(xv)
             with np.errstate(all="ignore"):
                 logx = B.const(np.log(x.c)) if base.support in ("positive", "simplex") else None
@@ -124,6 +123,8 @@ def compile_log_likelihood(model, args=(), kwargs=None, given=()):
                 terms = _ew_mixture(B, lower, base, np.asarray(x.c, np.float64).reshape(-1), s.name)
             elif isinstance(base, dist.MultivariateNormal):  # one observation per sample, as a Dirichlet vector
                 terms = _lp_mvn(B, lower, base, x, s)
+            elif isinstance(base, _ZERO_INFLATED):  # elementwise as it is: one value per observation
+                terms = _lp_zero_inflated(B, lower, base, x, s.name)
             else:
                 terms = _ELEMENTWISE.get(type(base), expand)(B, d, x, logx)
             # the constant terms are part of the answer: summed on the host, then added once (a scalar

@@ -117,10 +117,17 @@ LINALG_BASE = 32
 LINALG_OPCODES = ["cholesky", "trisolve"]
 OPCODE.update({n: LINALG_BASE + i for i, n in enumerate(LINALG_OPCODES)})
 CHOL_MAX_N = 128  # NMX_CHOL_MAX_N
+# enum nmx_special_opcode: elementwise binary ops numbered apart in the same way (after the dense ops)
+SPECIAL_BASE = 40
+SPECIAL_OPCODES = ["lrising", "logaddexp"]
+OPCODE.update({n: SPECIAL_BASE + i for i, n in enumerate(SPECIAL_OPCODES)})
+LRISING_SUM_MAX = 8  # NMX_LRISING_SUM_MAX
 
 
 def op_name(op):
-    """Name of an arithmetic opcode (nmx_opcode or nmx_linalg_opcode)."""
+    """Name of an arithmetic opcode (nmx_opcode, nmx_linalg_opcode or nmx_special_opcode)."""
+    if op >= SPECIAL_BASE:
+        return SPECIAL_OPCODES[op - SPECIAL_BASE]
     return LINALG_OPCODES[op - LINALG_BASE] if op >= LINALG_BASE else OPCODES[op]
 
 

@@ -9,7 +9,10 @@ builder: folding, sharing and refusals are the same) in which a site that is nei
 nor given is *drawn*: a draw op fills its slots with base variates (standard normal, exponential,
 Cauchy, uniform; gamma(concentration), Bernoulli(probs), Poisson(rate); Binomial(total_count,
 probs), the one draw with two parameters) and the existing arithmetic ops
-build the distribution from them (``_DRAW``).  A drawn site's value then parameterises the later
+build the distribution from them (``_DRAW``; ``_COUNT_DRAW`` for the count likelihoods: a gamma,
+exponential or beta draw feeds a Poisson or binomial draw, a Bernoulli draw of the gate zeroes a
+zero-inflated one; the outputs are integer sites, and an element whose mixed rate is at or above
+``POISSON_MAX_RATE`` is what ``draw_poisson`` gives there, NaN).  A drawn site's value then parameterises the later
 sites, so prior predictive of a hierarchical model runs ``mu -> theta -> obs`` in one program.
 One HIP kernel (csrc/predictive_program.hip) runs the program once per posterior sample.
 
@@ -30,7 +33,8 @@ from . import distributions as dist
 from . import native
 from .frontend import _base
 from .jnp import Sym, shape_of
-from .program import _LOGPROB, _ForwardProgram, _Refuse, _forward_prologue, _operand, _refuse
+from .program import (_COUNT_LOGPROB, _LOGPROB, _ZERO_INFLATABLE, _ZERO_INFLATED, _ForwardProgram, _Refuse,
+                      _forward_prologue, _logprob_entry, _operand, _refuse)
 
 _U24 = 5.9604644775390625e-08  # 2^-24
 
@@ -144,8 +148,74 @@ _DRAW = {
 # program has no such op, so they are supported with data only
 _UNDRAWABLE = (dist.CategoricalProbs, dist.CategoricalLogits, dist.MixtureSameFamily, dist.MultivariateNormal)
 assert set(_DRAW) | set(_UNDRAWABLE) == set(_LOGPROB) and not set(_DRAW) & set(_UNDRAWABLE)
+
+
+# ---- the count likelihoods (program.py _COUNT_LOGPROB), composed from the draw ops above: a gamma
+# (or exponential, or beta) draw of the latent rate (probability) feeds a Poisson (binomial) draw.
+# The mixed rate is itself random: where it reaches POISSON_MAX_RATE = 2^24 the element is what
+# draw_poisson documents there, NaN.  Kept apart from _DRAW, whose keys the draw tests pin.
+def _dr_gamma_poisson(B, d, n):
+    return B.draw("draw_poisson", n, B.draw("draw_gamma", n, d["concentration"]) / d["rate"])
+
+
+def _dr_negative_binomial2(B, d, n):
+    c = d["concentration"]
+    return B.draw("draw_poisson", n, B.draw("draw_gamma", n, c) * (d["mean"] / c))
+
+
+def _dr_negative_binomial_probs(B, d, n):
+    p = d["probs"]  # 1 / rate = p / (1 - p)
+    return B.draw("draw_poisson", n, B.draw("draw_gamma", n, d["total_count"]) * (p / (1.0 - p)))
+
+
+def _dr_negative_binomial_logits(B, d, n):
+    return B.draw("draw_poisson", n, B.draw("draw_gamma", n, d["total_count"]) * B.ew("exp", d["logits"]))
+
+
+def _dr_geometric_probs(B, d, n):
+    # the negative binomial of total_count 1: its gamma draw is an exponential one
+    p = d["probs"]
+    return B.draw("draw_poisson", n, B.draw("draw_exponential", n) * ((1.0 - p) / p))
+
+
+def _dr_geometric_logits(B, d, n):
+    return B.draw("draw_poisson", n, B.draw("draw_exponential", n) * B.ew("exp", -d["logits"]))
+
+
+def _dr_beta_binomial(B, d, n):
+    return B.draw("draw_binomial", n, _binomial_count(d), _dr_beta(B, d, n))
+
+
+_COUNT_DRAW = {
+    dist.GammaPoisson: _dr_gamma_poisson, dist.NegativeBinomial2: _dr_negative_binomial2,
+    dist.NegativeBinomialProbs: _dr_negative_binomial_probs, dist.NegativeBinomialLogits: _dr_negative_binomial_logits,
+    dist.GeometricProbs: _dr_geometric_probs, dist.GeometricLogits: _dr_geometric_logits,
+    dist.BetaBinomial: _dr_beta_binomial,
+}
+assert set(_COUNT_DRAW) | set(_ZERO_INFLATED) | {dist.ZeroInflatedPoisson} == set(_COUNT_LOGPROB)
+assert set(_ZERO_INFLATABLE) <= set(_DRAW) | set(_COUNT_DRAW)
+
+
+def _dr_zero_inflated(B, lower, base, n, site):
+    """(1 - b) * the base's draw, b a Bernoulli draw of the gate."""
+    inner = _base(base.base_dist)
+    if not isinstance(inner, _ZERO_INFLATABLE):
+        _refuse(site, f"a zero-inflated {type(inner).__name__} (supported bases: "
+                      f"{', '.join(t.__name__ for t in _ZERO_INFLATABLE)})")
+    d = {p: lower.vector(getattr(inner, p), site) for p in _logprob_entry(inner)[1]}
+    if isinstance(base, dist.ZeroInflatedLogits):
+        gate = 1.0 / (1.0 + B.ew("exp", -lower.vector(base.gate_logits, site)))
+    else:
+        gate = lower.vector(base.gate, site)
+    for p, val in list(d.items()) + [("gate", B.const(gate))]:
+        if val.n not in (1, n):
+            _refuse(site, f"parameter {p!r} of {val.n} elements at a site of {n}")
+    b = B.draw("draw_bernoulli", n, gate)
+    return (1.0 - b) * (_DRAW.get(type(inner)) or _COUNT_DRAW[type(inner)])(B, d, n)
+
+
 _INTEGER = (dist.BernoulliLogits, dist.BernoulliProbs, dist.Poisson, dist.BinomialProbs, dist.BinomialLogits,
-            dist.CategoricalProbs, dist.CategoricalLogits)
+            dist.CategoricalProbs, dist.CategoricalLogits) + tuple(_COUNT_LOGPROB)
 
 
 class Output:
@@ -480,11 +550,14 @@ def compile_predictive(model, args=(), kwargs=None, given=()):
             _refuse(s.name, f"a drawn site of {n} elements (more than 2^24, the draw counter's element field)")
         first = B.n_draws
         try:
-            d = {p: lower.vector(getattr(base, p), s.name) for p in _LOGPROB[type(base)][1]}
+            d = {p: lower.vector(getattr(base, p), s.name) for p in _logprob_entry(base)[1]}
             for p, val in d.items():
                 if val.n not in (1, n):
                     _refuse(s.name, f"parameter {p!r} of {val.n} elements at a site of {n}")
-            val = _DRAW[type(base)](B, d, n)
+            if isinstance(base, _ZERO_INFLATED):
+                val = _dr_zero_inflated(B, lower, base, n, s.name)
+            else:
+                val = (_DRAW.get(type(base)) or _COUNT_DRAW[type(base)])(B, d, n)
         except _Refuse:
             raise
         except NotImplementedError as e:

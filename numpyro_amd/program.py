@@ -26,7 +26,11 @@ sees u = log x and the program adds -sum(u), as NmxEightSchools does), ``unit_in
 HalfCauchy, HalfNormal, LogNormal, Exponential, Gamma, Uniform, Beta, Pareto, and one Dirichlet
 vector per site (``simplex``: K - 1 unconstrained coordinates, stick breaking built in log space
 from the cumsum and concat ops); observed sites from those plus BernoulliLogits / BernoulliProbs /
-Poisson / BinomialLogits / BinomialProbs (with a total_count that is data), CategoricalProbs /
+Poisson / BinomialLogits / BinomialProbs (with a total_count that is data), the count likelihoods of
+``_COUNT_LOGPROB`` (GammaPoisson, NegativeBinomialProbs / Logits, NegativeBinomial2, BetaBinomial,
+GeometricProbs / Logits, ZeroInflatedProbs / Logits over any of these: every parameter constant or
+symbolic, their lgamma(c + y) - lgamma(c) through the lrising op, zero inflation through logaddexp:
+include/numpyro_amd.h nmx_special_opcode), CategoricalProbs /
 CategoricalLogits (a parameter of rank 1) and MixtureSameFamily of a Categorical with univariate
 continuous components (the N x K table through a row-wise logsumexp); MultivariateNormal as an
 observed site (loc constant or symbolic) or as one latent vector (loc constant), its
@@ -56,6 +60,9 @@ from .potentials import LOWER, POSITIVE, REAL, SIMPLEX, UNIT, Potential
 
 _UNARY = ("neg", "exp", "log", "sqrt", "tanh", "log1p", "square", "softplus", "lgamma")
 _BINARY = ("add", "sub", "mul", "div", "pow")
+# the special ops (native.SPECIAL_OPCODES): elementwise and binary like _BINARY, with functions of their own
+_SPECIAL = ("lrising", "logaddexp")
+_TWO_OPERAND = _BINARY + _SPECIAL  # every elementwise op of two operands
 
 
 _DRAW_NAME = {v: k for k, v in native.DRAW_OPCODE.items()}
@@ -67,10 +74,75 @@ def _lgamma(x, dtype=np.float64):
     return torch.lgamma(torch.as_tensor(np.require(x, dtype, "C"))).numpy()
 
 
-def _digamma64(x):
+def _digamma(x):
+    """digamma in the dtype of x (float64, or float32 for the float32 restatement)."""
     import torch
 
-    return torch.special.digamma(torch.as_tensor(np.asarray(x, np.float64))).numpy()
+    x = np.asarray(x)
+    return torch.special.digamma(torch.as_tensor(np.require(x, x.dtype if x.dtype == np.float32 else np.float64,
+                                                            "C"))).numpy()
+
+
+# ---- the special ops, written once for float64 and float32 with the kernel's algorithm
+# (csrc/nmx_program.h nmx_lrising / nmx_lrising_da, include/numpyro_amd.h NMX_OP_LRISING)
+def _log1pmx(t, T):
+    """log1p(t) - t, t >= 0: the atanh series below 1/2 (nmx_log1pmx)."""
+    s = t / (T(2.0) + t)
+    s2 = s * s
+    odd = T(1 / 15) + s2 * T(1 / 17)
+    for d in (13, 11, 9, 7, 5, 3):
+        odd = T(1 / d) + s2 * odd
+    return np.where(t < T(0.5), s * (T(2.0) * s2 * odd - t), np.log1p(t) - t)
+
+
+def _stirling_s(x, T):
+    r = T(1.0) / x
+    r2 = r * r
+    return (T(1 / 12) - (T(1 / 360) - (T(1 / 1260) - T(1 / 1680) * r2) * r2) * r2) * r
+
+
+def _stirling_ds(x, T):
+    r = T(1.0) / x
+    r2 = r * r
+    return -r2 * (T(1 / 12) - r2 * (T(1 / 120) - r2 * (T(1 / 252) - r2 * T(1 / 240))))
+
+
+def _host_lrising(a, k, derivative=False):
+    """R(a, k) = lgamma(a + k) - lgamma(a) - k log(a), or dR/da = digamma(a + k) - digamma(a) - k / a,
+    in the dtype of the operands: whole k <= LRISING_SUM_MAX by sums over j < k, otherwise a shifted
+    up to x >= 8 and the Stirling difference through log1p(k / x) - k / x; NaN unless a > 0, k >= 0."""
+    a, k = np.broadcast_arrays(np.asarray(a), np.asarray(k))
+    T = np.result_type(a, k).type
+    a, k = a.astype(T), k.astype(T)
+    by_sum = (k <= T(native.LRISING_SUM_MAX)) & (k == np.floor(k))
+    total = np.zeros(a.shape, T)
+    for j in range(1, native.LRISING_SUM_MAX):
+        term = T(j) / (a * (a + T(j))) if derivative else np.log1p(T(j) / a)
+        total = total + np.where(T(j) < k, term, T(0.0))
+    x, shift, m = a.copy(), np.zeros(a.shape, T), np.zeros(a.shape, T)
+    for _ in range(8):
+        low = x < T(8.0)
+        term = k / (x * (x + k)) if derivative else np.log1p(k / x)
+        shift = shift + np.where(low, term, T(0.0))
+        x = np.where(low, x + T(1.0), x)
+        m = m + np.where(low, T(1.0), T(0.0))
+    t = k / x
+    if derivative:
+        body = _log1pmx(t, T) + T(0.5) * k / (x * (x + k)) + (_stirling_ds(x + k, T) - _stirling_ds(x, T))
+        out = np.where(by_sum, -total, body + (shift - k * m / (a * x)))
+    else:
+        body = x * _log1pmx(t, T) + (k - T(0.5)) * np.log1p(t) + (_stirling_s(x + k, T) - _stirling_s(x, T))
+        out = np.where(by_sum, total, body + (k * np.log1p(m / a) - shift))
+    return np.where((a > 0) & (k >= 0), out, T(np.nan))
+
+
+def _host_logaddexp(x, y):
+    """max + log1p(exp(-|x - y|)), the gap 0 where x == y (two -inf give -inf)."""
+    x, y = np.broadcast_arrays(np.asarray(x), np.asarray(y))
+    T = np.result_type(x, y).type
+    with np.errstate(invalid="ignore"):  # inf - inf where x == y, not taken
+        gap = np.where(x == y, T(0.0), -np.abs(x - y))
+    return (np.maximum(x, y) + np.log1p(np.exp(gap))).astype(T)
 
 
 _HOST_FWD = {
@@ -78,6 +150,7 @@ _HOST_FWD = {
     "square": np.square, "softplus": lambda x: np.maximum(x, 0.0) + np.log1p(np.exp(-np.abs(x))),
     "lgamma": _lgamma,
     "add": np.add, "sub": np.subtract, "mul": np.multiply, "div": np.divide, "pow": np.power,
+    "lrising": _host_lrising, "logaddexp": _host_logaddexp,
 }
 
 
@@ -100,7 +173,13 @@ def _host_rev(op, gd, x, y, out):
     if op == "softplus":
         return gd / (1.0 + np.exp(-x)), None
     if op == "lgamma":
-        return gd * _digamma64(x), None
+        return gd * _digamma(x), None
+    if op == "lrising":
+        return gd * _host_lrising(x, y, derivative=True), None
+    if op == "logaddexp":
+        dead = out == -np.inf
+        with np.errstate(invalid="ignore"):  # -inf - -inf where the result is dead, not taken
+            return np.where(dead, 0 * gd, gd * np.exp(x - out)), np.where(dead, 0 * gd, gd * np.exp(y - out))
     if op == "add":
         return gd, gd
     if op == "sub":
@@ -311,7 +390,7 @@ class Program:
                 op, dst, a, b, n, sa, sb, aux = o
                 if nm in _UNARY:
                     v[:, dst:dst + n] = fwd[nm](_operand(v, cp, a, n, sa))
-                elif nm in _BINARY:
+                elif nm in _TWO_OPERAND:
                     v[:, dst:dst + n] = fwd[nm](_operand(v, cp, a, n, sa), _operand(v, cp, b, n, sb))
                 elif nm == "reduce_sum":
                     v[:, dst] = v[:, a:a + n].sum(1)
@@ -329,24 +408,30 @@ class Program:
                     draw(nm, o, v)
         return v
 
-    def run_host(self, Z, f32_consts=False):
+    def run_host(self, Z, f32_consts=False, dtype=np.float64):
         """(U [C], dU/dz [C, D]) of the rows of Z [C, D], in float64: the program forward
         (_forward_host) and reverse, op by op as the kernel runs it.
-        ``f32_consts``: with the constant pool rounded to float32, as the device holds it."""
-        Z = np.atleast_2d(np.asarray(Z, np.float64))
+        ``f32_consts``: with the constant pool rounded to float32, as the device holds it.
+        ``dtype=np.float32``: the float32 restatement, every value, adjoint, constant and operation
+        in float32 (returned as float64): what float32 arithmetic alone costs."""
+        dtype = np.dtype(dtype).type
+        Z = np.atleast_2d(np.asarray(Z, dtype))
         C, S, D = Z.shape[0], self.num_slots, self.dim
-        cp = self.consts.astype(np.float64) if f32_consts else self.consts64
+        if dtype is np.float32:
+            cp = self.consts
+        else:
+            cp = self.consts.astype(np.float64) if f32_consts else self.consts64
         ix = self.index
-        v = self._forward_host(Z, np.float64, cp)
-        g = np.zeros((C, S))
+        v = self._forward_host(Z, dtype, cp)
+        g = np.zeros((C, S), dtype)
         g[:, S - 1] = 1.0
         with np.errstate(all="ignore"):
             for op, dst, a, b, n, sa, sb, aux in reversed(self.ops.tolist()):
                 nm = native.op_name(op)
                 gd = g[:, dst:dst + (1 if nm == "reduce_sum" else n)]
-                if nm in _UNARY or nm in _BINARY:
+                if nm in _UNARY or nm in _TWO_OPERAND:
                     x = _operand(v, cp, a, n, sa)
-                    y = _operand(v, cp, b, n, sb) if nm in _BINARY else None
+                    y = _operand(v, cp, b, n, sb) if nm in _TWO_OPERAND else None
                     da, db = _host_rev(nm, gd, x, y, v[:, dst:dst + n])
                     for ref, stride, d in ((a, sa, da), (b, sb, db)):
                         if d is None or ref < 0:
@@ -367,7 +452,7 @@ class Program:
                     _host_linalg_rev(nm, v, g, cp, dst, a, b, n, aux)
                 else:
                     _host_scan_rev(nm, v, g, dst, a, b, n, aux)
-        return v[:, S - 1].copy(), g[:, :D].copy()
+        return v[:, S - 1].astype(np.float64), g[:, :D].astype(np.float64)
 
     # ------------------------------------------------------------------ cost model
     def flops_per_eval(self, num_chains=1):
@@ -408,7 +493,7 @@ class Program:
             elif nm == "concat":
                 src = [ln for r, ln in ((a, aux), (b, n - aux)) if r >= 0]
             else:
-                src = [(n if s else 1) for r, s in ((a, sa), (b, sb) if nm in _BINARY else (-1, 0)) if r >= 0]
+                src = [(n if s else 1) for r, s in ((a, sa), (b, sb) if nm in _TWO_OPERAND else (-1, 0)) if r >= 0]
             nd = 1 if nm == "reduce_sum" else n
             el += sum(src) + nd  # forward
             el += nd + sum(src) + nd + 2 * sum(src)  # reverse: adjoint in, operands, result, adjoints +=
@@ -690,6 +775,15 @@ class _Builder:
     def unary(self, name):
         return lambda x: self.ew(name, x)
 
+    def lrising(self, a, k):
+        """lgamma(a + k) - lgamma(a) - k log(a) of the data k (the lrising op; 0 where every k is 0)."""
+        a, k = self.const(a), self.const(k)
+        if not k.is_const:
+            raise NotImplementedError("the step count of a log rising factorial depends on a latent site: it must be data")
+        if not a.is_const and np.all(k.c == 0.0):
+            return self.const(np.zeros(max(a.n, k.n)))
+        return self.ew("lrising", a, k)
+
     def draw(self, name, n, a=None, b=None):
         """A draw op of n elements (predictive programs only): never shared, never folded.  The
         stream id is the draw's ordinal."""
@@ -731,7 +825,7 @@ class _Builder:
         renumbered so that each defines the next free slots (draw ops: the next stream ids)."""
         ops, dim = self.ops, self.dim
         made = {o[1]: k for k, o in enumerate(ops)}
-        binary = range(OPCODE["add"], OPCODE["reduce_sum"])
+        binary = set(range(OPCODE["add"], OPCODE["reduce_sum"])) | {OPCODE[nm] for nm in _SPECIAL}
         draws = native.DRAW_OPCODE
 
         def fields(o):  # the words of an op that are operand references
@@ -1050,6 +1144,118 @@ def _ew_binomial_logits(B, d, x, logx):
 _ELEMENTWISE = {dist.CategoricalProbs: _ew_categorical_probs, dist.CategoricalLogits: _ew_categorical_logits,
                 dist.Dirichlet: _lp_dirichlet, dist.BernoulliLogits: _ew_bernoulli_logits,
                 dist.BinomialLogits: _ew_binomial_logits}
+# ---- count likelihoods (numpyro/distributions/conjugate.py, discrete.py).  Every log mass with a
+# concentration c holds lgamma(c + y) - lgamma(c), which cancels in float32 as a difference of two
+# lgamma ops; the lrising op gives R(c, y) = lgamma(c + y) - lgamma(c) - y log(c), which tends to 0
+# as c grows, and the y log(c) it leaves out joins the other logarithms so that the near-Poisson
+# (near-binomial) limit has no large terms of opposite sign:
+#   GammaPoisson(c, mean m = c / rate):  R(c, y) + y log(m) - (c + y) log1p(m / c) - log y!
+def _log_factorial(B, x):
+    return B.ew("lgamma", x + 1.0)  # data alone: folded on the host
+
+
+def _lp_gamma_poisson(B, d, x, logx):
+    c, rate = d["concentration"], d["rate"]
+    return [B.lrising(c, x), x * B.ew("log", c / rate), -((c + x) * B.ew("log1p", 1.0 / rate)), -_log_factorial(B, x)]
+
+
+def _lp_negative_binomial2(B, d, x, logx):
+    c, m = d["concentration"], d["mean"]
+    return [B.lrising(c, x), x * B.ew("log", m), -((c + x) * B.ew("log1p", m / c)), -_log_factorial(B, x)]
+
+
+def _lp_negative_binomial_probs(B, d, x, logx):
+    # rate = 1 / p - 1: log1p(1 / rate) = -log1p(-p) and the mean is n p / (1 - p)
+    n, p = d["total_count"], d["probs"]
+    return [B.lrising(n, x), x * B.ew("log", n * p), n * B.ew("log1p", -p), -_log_factorial(B, x)]
+
+
+def _lp_negative_binomial_logits(B, d, x, logx):
+    # the reference's -(n softplus(logits) + y softplus(-logits) + log_beta_1(n, y))
+    n, lg = d["total_count"], d["logits"]
+    return [B.lrising(n, x), x * B.ew("log", n), -(x * B.ew("softplus", -lg)), -(n * B.ew("softplus", lg)),
+            -_log_factorial(B, x)]
+
+
+def _lp_beta_binomial(B, d, x, logx):
+    # C(n, y) B(c1 + y, c0 + n - y) / B(c1, c0) as three rising factorials; what they leave out is
+    # y log(c1 / (c1 + c0)) + (n - y) log(c0 / (c1 + c0)), the binomial limit, each through a log1p
+    c1, c0, n = d["concentration1"], d["concentration0"], d["total_count"]
+    return [B.lrising(c1, x), B.lrising(c0, n - x), -B.lrising(c1 + c0, n),
+            -(x * B.ew("log1p", c0 / c1)), -((n - x) * B.ew("log1p", c1 / c0)), _binomial_coefficient(B, n, x)]
+
+
+def _lp_geometric_probs(B, d, x, logx):
+    p = d["probs"]
+    return [x * B.ew("log1p", -p), B.ew("log", p)]
+
+
+def _lp_geometric_logits(B, d, x, logx):
+    lg = d["logits"]
+    return [-((x + 1.0) * B.ew("softplus", lg)), lg]
+
+
+def _lp_zero_inflated(B, lower, base, x, site):
+    """ZeroInflatedProbs / ZeroInflatedLogits at the observations x: with lg = log gate, l1 =
+    log(1 - gate) and lp the base's elementwise log mass, l1 + lp where y > 0 and
+    logaddexp(lg, l1 + lp) where y = 0 (the reference's ZeroInflatedLogits algebra), the two joined
+    by the data's 0 / 1 mask.  Both branches are finite at every y for the bases accepted here.  The
+    base's data-only terms (log y!, the binomial coefficient) stay host constants."""
+    inner = _base(base.base_dist)
+    entry = _logprob_entry(inner)
+    if entry is None or not isinstance(inner, _ZERO_INFLATABLE):
+        _refuse(site, f"a zero-inflated {type(inner).__name__} (supported bases: "
+                      f"{', '.join(t.__name__ for t in _ZERO_INFLATABLE)})")
+    d = {p: lower.vector(getattr(inner, p), site) for p in entry[1]}
+    _check_count_data(inner, d, site)
+    if isinstance(base, dist.ZeroInflatedLogits):
+        gl = lower.vector(base.gate_logits, site)
+        log_gate, log_1m = -B.ew("softplus", -gl), -B.ew("softplus", gl)
+    else:
+        gate = lower.vector(base.gate, site)
+        log_gate, log_1m = B.ew("log", gate), B.ew("log1p", -gate)
+    dyn, cst = log_1m, B.const(np.zeros(1))
+    for t in _ELEMENTWISE.get(type(inner), entry[0])(B, d, x, None):
+        t = B.const(t)
+        if t.is_const:
+            cst = cst + t
+        else:
+            dyn = dyn + t
+    zero = B.const((x.c == 0.0).astype(np.float64))
+    return [zero * B.ew("logaddexp", log_gate, dyn + zero * cst), (1.0 - zero) * dyn, (1.0 - zero) * cst]
+
+
+# distribution -> (expansion, parameter names, may be latent), as _LOGPROB, whose keys existing
+# tests pin: the lowering consults this table after it (_logprob_entry)
+_COUNT_LOGPROB = {
+    dist.GammaPoisson: (_lp_gamma_poisson, ("concentration", "rate"), False),
+    dist.NegativeBinomial2: (_lp_negative_binomial2, ("mean", "concentration"), False),
+    dist.NegativeBinomialProbs: (_lp_negative_binomial_probs, ("total_count", "probs"), False),
+    dist.NegativeBinomialLogits: (_lp_negative_binomial_logits, ("total_count", "logits"), False),
+    dist.BetaBinomial: (_lp_beta_binomial, ("concentration1", "concentration0", "total_count"), False),
+    dist.GeometricProbs: (_lp_geometric_probs, ("probs",), False),
+    dist.GeometricLogits: (_lp_geometric_logits, ("logits",), False),
+    dist.ZeroInflatedProbs: (None, (), False),  # _lp_zero_inflated lowers the gate and the base it holds
+    dist.ZeroInflatedLogits: (None, (), False),
+    dist.ZeroInflatedPoisson: (None, (), False),
+}
+_ZERO_INFLATED = (dist.ZeroInflatedProbs, dist.ZeroInflatedLogits)
+_ZERO_INFLATABLE = (dist.Poisson, dist.GammaPoisson, dist.NegativeBinomial2, dist.NegativeBinomialProbs,
+                    dist.NegativeBinomialLogits, dist.GeometricProbs, dist.GeometricLogits, dist.BinomialProbs,
+                    dist.BinomialLogits, dist.BetaBinomial)
+
+
+def _logprob_entry(base):
+    """The (expansion, parameter names, may be latent) of a distribution, or None."""
+    return _LOGPROB.get(type(base)) or _COUNT_LOGPROB.get(type(base))
+
+
+def _check_count_data(base, d, site):
+    """Binomial and BetaBinomial take their total_count as data."""
+    if isinstance(base, _BINOMIAL + (dist.BetaBinomial,)) and not d["total_count"].is_const:
+        _refuse(site, "a total_count that depends on a latent site: it must be data")
+
+
 # support -> transform code of a latent site
 _SUPPORT_CODE = {"real": REAL, "positive": POSITIVE, "unit_interval": UNIT, "interval": UNIT, "greater_than": LOWER,
                  "simplex": SIMPLEX}
@@ -1127,7 +1333,7 @@ class _Lowering:
             return B.ew(op, self(x.args[0], site))
         if op == "expit":  # exp(-softplus(-x)): log(expit(x)) then folds to -softplus(-x)
             return B.ew("exp", B.ew("neg", B.ew("softplus", B.ew("neg", self(x.args[0], site)))))
-        if op in _BINARY:
+        if op in _BINARY or op == "logaddexp":
             return B.ew(op, *(self._broadcast(a, x.shape, site) for a in x.args))
         if op == "cholesky":
             return B.cholesky(self(x.args[0], site), x.shape[0])
@@ -1169,7 +1375,7 @@ class _Lowering:
                 _refuse(site, f"matmul of shapes {np.shape(_host(a)) if not isinstance(a, Sym) else a.shape} and "
                               f"{np.shape(_host(b)) if not isinstance(b, Sym) else b.shape}")
             return B.matvec(M, vec)
-        _refuse(site, f"operation {op!r} is not supported (supported: {sorted(_UNARY[:7] + _BINARY)}, expit, sum, "
+        _refuse(site, f"operation {op!r} is not supported (supported: {sorted(_UNARY[:7] + _BINARY)}, expit, logaddexp, sum, "
                       "cumsum, logsumexp, concatenate, getitem, matmul, linalg.cholesky)")
 
     def _broadcast(self, a, out_shape, site):
@@ -1207,7 +1413,7 @@ def _forward_prologue(model, args, kwargs, given, missing, observed=lambda s: No
     sizes = {}
     for s in trace.sites.values():
         base = _base(s.fn)
-        if type(base) not in _LOGPROB:
+        if _logprob_entry(base) is None:
             _refuse(s.name, f"{type(base).__name__} is not supported")
         if s.obs is None and s.name not in given:
             missing(s, base)
@@ -1241,7 +1447,7 @@ def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
         base = _base(s.fn)
         if len(s.shape) > 1:
             _refuse(s.name, f"latent of shape {s.shape}: latents of rank > 1 are not supported")
-        entry = _LOGPROB.get(type(base))
+        entry = _logprob_entry(base)
         if entry is None or not entry[2]:
             _refuse(s.name, f"{type(base).__name__} is not supported as a latent site")
         if base.support not in _SUPPORT_CODE:
@@ -1301,14 +1507,13 @@ def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
     scalars = []  # scalar terms of log p + log|J|
     for s in trace.sites.values():
         base = _base(s.fn)
-        entry = _LOGPROB.get(type(base))
+        entry = _logprob_entry(base)
         if entry is None:
             _refuse(s.name, f"{type(base).__name__} is not supported")
         expand, pnames, _ = entry
         try:
             d = {p: lower.vector(getattr(base, p), s.name) for p in pnames}
-            if isinstance(base, _BINOMIAL) and not d["total_count"].is_const:
-                _refuse(s.name, "a total_count that depends on a latent site: it must be data")
+            _check_count_data(base, d, s.name)
             if s.obs is None:
                 x = constrained[s.name]
                 logx = log_value[s.name]
@@ -1327,6 +1532,8 @@ def compile_model(model, args=(), kwargs=None, max_workspace_bytes=1 << 30):
                 terms = _lp_mixture(B, lower, base, np.asarray(x.c, np.float64).reshape(-1), s.name)
             elif isinstance(base, dist.MultivariateNormal):
                 terms = _lp_mvn(B, lower, base, x, s)
+            elif isinstance(base, _ZERO_INFLATED):
+                terms = _lp_zero_inflated(B, lower, base, x, s.name)
             else:
                 terms = expand(B, d, x, logx)
             if s.obs is None:
