@@ -389,7 +389,7 @@ class HMC(MCMCKernel):
                                chain_offset=chain_offset)
         ip = None
         if init_params is not None:
-            ip = _flatten_init(eng.potential, init_params, int(num_chains))
+            ip = _flatten_init(eng.model_potential, init_params, int(num_chains))
             ip = torch.as_tensor(ip, dtype=torch.float32)
             if ip.dim() == 1:
                 ip = ip[None, :].expand(eng.C, -1)

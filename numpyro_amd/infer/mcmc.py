@@ -166,7 +166,10 @@ class MCMC:
 
         from .hmc import _args_key
 
-        key = (id(self.sampler), _args_key(args, kwargs), tuple(str(d) for d in devs))
+        # a callable potential_fn is re-bound when init_params change structure (bind_potential_fn):
+        # the engines of the old potential, and its dimension, go with it -- as in _get_engine
+        key = (id(self.sampler), _args_key(args, kwargs), tuple(str(d) for d in devs),
+               id(getattr(self.sampler, "_potential", None)) if getattr(self.sampler, "_potential_fn", None) else 0)
         if self._engines is None or self._engine_key != key:
             engines = []
             pot_fn = getattr(self.sampler, "_potential_fn", None)
@@ -230,6 +233,22 @@ class MCMC:
             self._run(rng_key, args, kwargs, extra_fields, init_params,
                       n_iter=self.num_warmup + self.num_samples, lower=self.num_warmup)
 
+    def _init_rows(self, pot, init_params):
+        """init_params -> the [local_chains, D] float32 rows of this process's chains.  `pot` is the
+        model's potential (Engine.model_potential, not a whitening wrapper around it).  All
+        num_chains chains are flattened -- a [D] value is every chain's start -- and a process
+        that holds a shard of them (torch.distributed) keeps rows [chain_lo, chain_hi)."""
+        from .hmc import _flatten_init
+
+        ip = torch.as_tensor(_flatten_init(pot, init_params, self.num_chains), dtype=torch.float32)
+        if ip.dim() == 1:
+            ip = ip[None, :].expand(self.num_chains, -1)
+        if ip.shape[0] == self.num_chains and self.local_chains != self.num_chains:
+            ip = ip[self.chain_lo:self.chain_hi]
+        if ip.dim() != 2 or ip.shape[0] != self.local_chains:
+            raise ValueError("`init_params` must have the same leading dimension as `num_chains`.")
+        return ip
+
     def _run(self, rng_key, args, kwargs, extra_fields, init_params, n_iter, lower, resume=None):
         assert isinstance(extra_fields, (tuple, list))
         collect, derived = [], []
@@ -259,7 +278,9 @@ class MCMC:
         seed = key_to_seed(rng_key)
         bind = getattr(self.sampler, "bind_potential_fn", None)
         if bind is not None and resume is None:
-            bind(init_params, self.local_chains)
+            # the global chain count decides whether init_params carry a chain axis (the
+            # reference's rule: batched when num_chains > 1), not this process's shard of it
+            bind(init_params, self.num_chains)
         devs = self._run_devices()
         if devs is not None:
             return self._run_multi(devs, seed, args, kwargs, init_params, n_iter, lower, resume)
@@ -271,18 +292,7 @@ class MCMC:
             if resume is not None:
                 self._restore(eng, resume)
             else:
-                ip = None
-                if init_params is not None:
-                    from .hmc import _flatten_init
-
-                    ip = torch.as_tensor(_flatten_init(eng.potential, init_params, self.local_chains),
-                                         dtype=torch.float32)
-                    if ip.dim() == 1:
-                        ip = ip[None, :].expand(eng.C, -1)
-                    if ip.shape[0] == self.num_chains and self.local_chains != self.num_chains:
-                        ip = ip[self.chain_lo:self.chain_hi]
-                    if ip.shape[0] != eng.C:
-                        raise ValueError("`init_params` must have the same leading dimension as `num_chains`.")
+                ip = None if init_params is None else self._init_rows(eng.model_potential, init_params)
                 eng.initialize(seed, self.num_warmup, init_params=ip, radius=self.sampler.init_radius())
             start = torch.cuda.Event(enable_timing=True)
             end = torch.cuda.Event(enable_timing=True)
@@ -309,14 +319,7 @@ class MCMC:
         G = len(engines)
         ip_all = None
         if resume is None and init_params is not None:
-            from .hmc import _flatten_init
-
-            ip_all = torch.as_tensor(_flatten_init(engines[0].potential, init_params, self.local_chains),
-                                     dtype=torch.float32)
-            if ip_all.dim() == 1:
-                ip_all = ip_all[None, :].expand(self.local_chains, -1)
-            if ip_all.shape[0] != self.local_chains:
-                raise ValueError("`init_params` must have the same leading dimension as `num_chains`.")
+            ip_all = self._init_rows(engines[0].model_potential, init_params)
         parts = None
         if resume is not None:
             parts = getattr(resume, "_parts", None)

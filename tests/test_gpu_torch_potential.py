@@ -6,6 +6,8 @@ its gradient with torch.func on the engine's compacted list (generic path, no fu
 * the same target as a fused kernel (diagonal normal): the same trees and draws to rounding;
 * a target no fused kernel covers (a banana), against its known moments;
 * init_params required (hmc.py:754-757), array-valued z returned as an array, dense mass."""
+import contextlib
+
 import numpy as np
 import pytest
 import torch
@@ -81,3 +83,24 @@ def test_torch_potential_needs_init_params_and_runs_dense(device):
     assert float(err.max()) < 0.15
     imm = mcmc.last_state.adapt_state.inverse_mass_matrix
     assert imm.shape == (C, 5, 5)
+    # one chain takes the reference's unbatched init_params behind the whitening wrapper too
+    mcmc = MCMC(NUTS(potential_fn=diag_fn, dense_mass=True), num_warmup=30, num_samples=10, num_chains=1,
+                progress_bar=False)
+    mcmc.run(2, init_params={"x": torch.zeros(5)})
+    x = mcmc.get_samples()["x"]
+    assert mcmc._engine.D == 5 and x.shape == (10, 5) and bool(torch.isfinite(x).all())
+    assert mcmc.last_state.adapt_state.inverse_mass_matrix.shape == (1, 5, 5)
+
+    # an array-valued z of shape (2, 3): unbatched for one chain, [C, 2, 3] for more, per-chain and pooled
+    def grid_fn(z):
+        return 0.5 * (((z - MU.to(z.device).repeat(2)[:6].reshape(2, 3)) / 0.7) ** 2).sum()
+
+    for dense in (True, "pooled"):
+        for C1, ip in ((1, torch.zeros(2, 3)), (4, torch.arange(24.0).reshape(4, 2, 3) / 24)):
+            with pytest.warns(UserWarning) if dense == "pooled" else contextlib.nullcontext():
+                kern = NUTS(potential_fn=grid_fn, dense_mass=dense)
+            mcmc = MCMC(kern, num_warmup=30, num_samples=10, num_chains=C1, progress_bar=False)
+            mcmc.run(2, init_params=ip)
+            assert mcmc._engine.D == 6 and mcmc._engine.C == C1
+            x = mcmc.get_samples(group_by_chain=True)
+            assert torch.is_tensor(x) and x.shape == (C1, 10, 2, 3) and bool(torch.isfinite(x).all())
