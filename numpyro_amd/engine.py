@@ -15,7 +15,7 @@ import contextlib
 import ctypes
 import math
 import uuid
-from dataclasses import dataclass
+from dataclasses import dataclass, field, replace
 
 import torch
 
@@ -55,6 +55,71 @@ def build_adaptation_schedule(num_steps):
         schedule.append((cur_start, next_start - 1))
     schedule.append((end_window_start, num_steps - 1))
     return schedule
+
+
+def middle_windows(num_warmup):
+    """The middle adaptation windows as (start, end + 1) (hmc_util.py:596-635): every window but
+    the first and the last of the schedule; none without warmup."""
+    sched = build_adaptation_schedule(num_warmup) if num_warmup > 0 else []
+    return [(ws, we + 1) for ws, we in sched[1:-1]]
+
+
+@dataclass
+class CollectPlan:
+    """What one run() call collects and how it is driven: transition i >= cstart completes slot
+    (i - cstart) // thinning of `samples` [S, D, ldc] and `fields` [S, NC, ldc] (fori_collect,
+    util.py:330-346: the last write wins).  Built once in run(); the unthinned chunks of a
+    dense-mass window are a second plan over their own buffers."""
+    seed: int
+    stream: int
+    poll_every: int = 16
+    cstart: int = 0
+    thinning: int = 1
+    S: int = 0
+    samples: torch.Tensor | None = None
+    fields: torch.Tensor | None = None
+    codes: torch.Tensor | None = None  # transforms the step kernels apply to collected draws (_collect_codes)
+
+    def slot_of(self, i):
+        """Collection slot whose final value transition i writes, or -1."""
+        off = i - self.cstart
+        if off < 0 or off % self.thinning != self.thinning - 1 or off // self.thinning >= self.S:
+            return -1
+        return off // self.thinning
+
+    def slots_in(self, a, b):
+        """Collection slots completed by transitions [a, b)."""
+        return [k for k in map(self.slot_of, range(a, b)) if k >= 0]
+
+    def put(self, slot, z, positive):
+        """A model-space draw z [D, ldc] into a slot, constrained: exp on the `positive` rows."""
+        if self.samples.shape[0] == 0:  # only the fields are collected
+            return
+        self.samples[slot].copy_(z)
+        if bool(positive.any()):
+            self.samples[slot][positive] = torch.exp(self.samples[slot][positive])
+
+    def pointers(self):
+        """(samples or None, fields, codes) as the step kernels take them."""
+        return ptr(self.samples) if self.samples.shape[0] else None, ptr(self.fields), ptr(self.codes)
+
+
+@dataclass
+class Lane:
+    """One stream of the launched loop: the chains of one group (or all of them), their two
+    compacted lists (by parity), the word that counts their DONE chains, and `advance`, which
+    launches one leaf for them.  The count is polled without blocking: copied to a pinned word
+    behind an event, read on the next round."""
+    cfg: NutsConfig
+    lists: list
+    stream: object  # torch stream the DONE count is polled on; None: the current stream
+    done: torch.Tensor
+    size: int
+    advance: object
+    live: bool = True  # some chain of the lane is not DONE, as far as the last poll showed
+    pending: bool = False
+    host: torch.Tensor = field(default_factory=lambda: torch.zeros(1, dtype=torch.int32, pin_memory=True))
+    event: object = field(default_factory=torch.cuda.Event)
 
 
 @dataclass
@@ -223,8 +288,9 @@ class Engine:
         return t
 
     # ------------------------------------------------------------------ config
-    def _fill_cfg(self, iter_begin, iter_end, num_warmup, seed, collect_start, thinning, collection_size):
+    def _fill_cfg(self, iter_begin, iter_end, plan):
         o, c = self.opts, self.cfg
+        num_warmup = self.num_warmup
         c.algo = o.algo
         c.num_chains = self.C
         c.dim = self.D
@@ -252,11 +318,11 @@ class Engine:
         c.num_windows = len(sched)
         for i in range(native.MAX_WINDOWS):
             c.window_end[i] = sched[i][1] if i < len(sched) else -1
-        c.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        c.seed = int(plan.seed) & 0xFFFFFFFFFFFFFFFF
         c.chain_offset = self.chain_offset
-        c.collect_start = int(collect_start)
-        c.collect_thinning = int(thinning)
-        c.collection_size = int(collection_size)
+        c.collect_start = int(plan.cstart)
+        c.collect_thinning = int(plan.thinning)
+        c.collection_size = int(plan.S)
         c.ldc = self.ldc
         c.layout = native.LAYOUT_CHAIN_ROWS if self.crow else native.LAYOUT_CHAIN_MINOR
         tr = self._trace
@@ -299,7 +365,7 @@ class Engine:
         self.generation = next(_generations)
         self.num_warmup = int(num_warmup)
         self._alloc(self.iter_capacity)
-        self._fill_cfg(0, 0, num_warmup, seed, 0, 1, 0)
+        self._fill_cfg(0, 0, CollectPlan(seed, s))
         imm = self.init_inverse_mass_matrix
         imm_t = None
         if self.dense:
@@ -317,20 +383,13 @@ class Engine:
             z = z.reshape(self.C, self.D)
             zt = torch.zeros(self.D, self.ldc, dtype=torch.float32, device=self.device)
             zt[:, :self.C] = z.t()
-            check(lib().nmx_nuts_init_from(ctypes.byref(self.cfg), ptr(self.arena), ptr(zt), s))
-            self._evaluate_all(s)
-            check(lib().nmx_nuts_init_check(ctypes.byref(self.cfg), ptr(self.arena), s))
-            bad = int(self.view("counters")[1].item())
+            bad = self._place_chains(s, zt)
             if bad:
                 raise RuntimeError(f"Cannot find valid initial parameters: {bad} chains have "
                                    "non-finite potential energy or gradient at init_params.")
         else:
             for attempt in range(INIT_ATTEMPTS):
-                check(lib().nmx_nuts_init_draw(ctypes.byref(self.cfg), ptr(self.arena), attempt,
-                                               float(radius), s))
-                self._evaluate_all(s)
-                check(lib().nmx_nuts_init_check(ctypes.byref(self.cfg), ptr(self.arena), s))
-                if int(self.view("counters")[1].item()) == 0:
+                if self._place_chains(s, attempt=attempt, radius=radius) == 0:
                     break
             else:
                 raise RuntimeError("Cannot find valid initial parameters. Please check your model "
@@ -342,6 +401,19 @@ class Engine:
         if self._heuristic():
             self._find_step_size(True, s)
         self.generation = next(_generations)
+
+    def _place_chains(self, s, z=None, attempt=0, radius=2.0):
+        """Set every chain's position -- to z [D, ldc], or to draw `attempt` of the uniform
+        initial points -- and evaluate the potential there; returns how many chains have a
+        non-finite potential energy or gradient."""
+        cfgp, arena = ctypes.byref(self.cfg), ptr(self.arena)
+        if z is not None:
+            check(lib().nmx_nuts_init_from(cfgp, arena, ptr(z), s))
+        else:
+            check(lib().nmx_nuts_init_draw(cfgp, arena, attempt, float(radius), s))
+        self._evaluate_all(s)
+        check(lib().nmx_nuts_init_check(cfgp, arena, s))
+        return int(self.view("counters")[1].item())
 
     def _evaluate_all(self, s):
         """The potential at z_eval of every chain with phase >= LEAF (initial points).  The
@@ -361,7 +433,7 @@ class Engine:
     def _heuristic(self):
         # wa_init searches whenever adapt_step_size is set, num_warmup = 0 included
         # (hmc.py:319-339 -> hmc_util.py:572-576); the window-end searches exist only with
-        # middle windows (_window_ends is empty without warmup)
+        # middle windows (middle_windows is empty without warmup)
         o = self.opts
         return bool(o.find_heuristic_step_size) and bool(o.adapt_step_size)
 
@@ -405,23 +477,14 @@ class Engine:
                 wt.product(fwd, ptr(x), ptr(o), None, None, None, self.C, self.ldc, s)
         return a
 
-    def _search_at_window_end(self, e, cstart, thinning, S, fields, s):
+    def _search_at_window_end(self, plan, e):
         """find_reasonable_step_size at the end of a middle window (hmc_util.py:619-626); the
         transition that ended the window reports the searched step size, as its adapt_state
         does in the reference (update_fn returns it, :700-705)."""
-        self._find_step_size(False, s)
-        slot = self._slot_of(e - 1, cstart, thinning, S)
+        self._find_step_size(False, plan.stream)
+        slot = plan.slot_of(e - 1)
         if slot >= 0:
-            fields[slot, native.COLLECT.index("step_size"), :self.C] = self.view("step_size")[:self.C]
-
-    def _search_cuts(self, a, b):
-        """Window ends e in (a, b] at which the step-size search runs (sorted)."""
-        return [e for e in self._window_ends() if a < e <= b] if self._heuristic() else []
-
-    def _window_ends(self):
-        """First transition index after each middle adaptation window (hmc_util.py:596-635)."""
-        sched = build_adaptation_schedule(self.num_warmup)
-        return [we + 1 for i, (_, we) in enumerate(sched) if 0 < i < len(sched) - 1]
+            plan.fields[slot, native.COLLECT.index("step_size"), :self.C] = self.view("step_size")[:self.C]
 
     def _reexpress(self, inverse_mass_matrix, mu, s):
         """Change the whitening of every chain (at an iteration boundary): z is kept,
@@ -435,10 +498,7 @@ class Engine:
             wt.set(inverse_mass_matrix, mu)
             w[:, :self.C] = wt.to_whitened(z[:, :self.C])
             torch.cuda.current_stream(self.device).synchronize()
-        check(lib().nmx_nuts_init_from(ctypes.byref(self.cfg), ptr(self.arena), ptr(w), s))
-        self._evaluate_all(s)
-        check(lib().nmx_nuts_init_check(ctypes.byref(self.cfg), ptr(self.arena), s))
-        bad = int(self.view("counters")[1].item())
+        bad = self._place_chains(s, w)
         if bad:
             raise RuntimeError(f"{bad} chains have a non-finite potential after the mass-matrix update")
 
@@ -459,29 +519,23 @@ class Engine:
         keep = (tr == POSITIVE) if self.constrain_samples else torch.zeros_like(tr, dtype=torch.bool)
         return torch.where(keep, tr, torch.zeros_like(tr))
 
-    def _convert_slots(self, samples, slots, s):
-        """In place: whitened draws of collection slots -> model space -> constrained."""
-        if len(slots) == 0 or samples.shape[0] == 0:
+    def _convert_slots(self, plan, a, b):
+        """In place: the whitened draws that transitions [a, b) collected -> model space ->
+        constrained."""
+        slots = plan.slots_in(a, b)
+        if len(slots) == 0 or plan.samples.shape[0] == 0:
             return
-        wt = self.potential.whitening
         tmp = torch.empty(self.D, self.ldc, dtype=torch.float32, device=self.device)
         pos = self._positive()
         for k in slots:
-            wt.to_model(samples[k], tmp, stream=s)
-            samples[k].copy_(tmp)
-            if bool(pos.any()):
-                samples[k][pos] = torch.exp(samples[k][pos])
+            self.potential.whitening.to_model(plan.samples[k], tmp, stream=plan.stream)
+            plan.put(k, tmp, pos)
 
     def _dense_segments(self, it0, it1):
         """Split [it0, it1) at the bounds of the middle adaptation windows; yields
         (a, b, window) with window = (start, end + 1) of the middle window holding [a, b), or
         None outside them."""
-        bounds = []
-        if self.opts.adapt_mass_matrix and self.num_warmup > 0:
-            sched = build_adaptation_schedule(self.num_warmup)
-            for i, (ws, we) in enumerate(sched):
-                if 0 < i < len(sched) - 1:
-                    bounds.append((ws, we + 1))
+        bounds = middle_windows(self.num_warmup) if self.opts.adapt_mass_matrix else []
         segs, a = [], it0
         for ws, we1 in bounds:
             if we1 <= a or ws >= it1:
@@ -496,9 +550,21 @@ class Engine:
             segs.append((a, it1, None))
         return segs
 
+    def _segments(self, it0, it1):
+        """The run plan of [it0, it1) for both mass modes: (a, b, window, search_at_b) in order.
+        `window` is the middle window whose draws [a, b) adds to the dense-mass pool (None:
+        diagonal mass, or outside the adapted windows); the step-size search, when it is on,
+        runs at every middle-window end b in (it0, it1], where a segment always ends."""
+        cuts = {e for _, e in middle_windows(self.num_warmup) if it0 < e <= it1} if self._heuristic() else set()
+        pieces = self._dense_segments(it0, it1) if self.dense else [(it0, it1, None)]
+        segs = []
+        for a, b, win in pieces:
+            ends = sorted({e for e in cuts if a < e < b} | {b})
+            segs += [(p, q, win, q in cuts) for p, q in zip([a] + ends[:-1], ends) if q > p]
+        return segs
+
     def run(self, num_iters: int, seed: int, collect_begin: int = 0, collection_size: int | None = None,
-            thinning: int = 1, poll_every: int = 16, stream=None, max_launches: int | None = None,
-            collect_samples: bool = True):
+            thinning: int = 1, poll_every: int = 16, stream=None, collect_samples: bool = True):
         """Advance every chain by `num_iters` transitions.  Transitions with relative index
         i >= start_idx (fori_collect semantics) are collected into the returned buffers.
         Returns (samples [S, D, ldc], fields [S, NC, ldc], launches); with collect_samples
@@ -513,29 +579,22 @@ class Engine:
         if self.sync_chains and num_iters > self.iter_capacity:
             self._grow_finished(num_iters)
         S = max(int(collection_size), 0)
-        if S > 0:
-            samples = torch.empty((S if collect_samples else 0, self.D, self.ldc), dtype=torch.float32,
-                                  device=self.device)
-            fields = torch.zeros((S, len(native.COLLECT), self.ldc), dtype=torch.float32, device=self.device)
-        else:  # nothing is collected: the device writes no slot (collection_size 0)
-            samples = torch.empty((0, self.D, self.ldc), dtype=torch.float32, device=self.device)
-            fields = torch.empty((0, len(native.COLLECT), self.ldc), dtype=torch.float32, device=self.device)
+        # S = 0: nothing is collected, the device writes no slot (collection_size 0)
+        samples = torch.empty((S if collect_samples else 0, self.D, self.ldc), dtype=torch.float32,
+                              device=self.device)
+        fields = torch.zeros((S, len(native.COLLECT), self.ldc), dtype=torch.float32, device=self.device)
         self.generation = next(_generations)
-        cstart = it0 + start_idx
-        if not self.dense:
-            # with the step-size search, stop at every middle-window end it runs at
-            cuts = self._search_cuts(it0, it0 + num_iters)
-            launches, a = 0, it0
-            for b in sorted(set(cuts + [it0 + num_iters])):
-                if b > a:
-                    launches += self._run_segment(a, b, seed, cstart, thinning, S, samples, fields, poll_every, s,
-                                                  max_launches)
-                if b in cuts:
-                    self._search_at_window_end(b, cstart, thinning, S, fields, s)
-                a = b
-        else:
-            launches = self._run_dense(it0, it0 + num_iters, seed, cstart, thinning, S, samples, fields,
-                                       poll_every, s, max_launches)
+        plan = CollectPlan(seed, s, poll_every, it0 + start_idx, thinning, S, samples, fields, self._collect_codes())
+        launches = 0
+        for a, b, win, search in self._segments(it0, it0 + num_iters):
+            if win is not None:
+                launches += self._run_window(plan, a, b, win)
+            else:
+                launches += self._run_segment(plan, a, b)
+                if self.dense:
+                    self._convert_slots(plan, a, b)
+            if search:
+                self._search_at_window_end(plan, b)
         self.iteration = it0 + num_iters
         self.generation = next(_generations)
         return samples, fields, launches
@@ -544,73 +603,52 @@ class Engine:
     def _slot_of(i, cstart, thinning, S):
         """Collection slot whose final value transition i writes (util.py:330-346: slot
         (i - start) // thinning, last write wins), or -1."""
-        off = i - cstart
-        if off < 0 or off % thinning != thinning - 1 or off // thinning >= S:
-            return -1
-        return off // thinning
+        return CollectPlan(0, 0, cstart=cstart, thinning=thinning, S=S).slot_of(i)
 
-    def _slots_in(self, a, b, cstart, thinning, S):
-        """Collection slots completed by transitions [a, b)."""
-        return [k for k in (self._slot_of(i, cstart, thinning, S) for i in range(a, b)) if k >= 0]
-
-    def _run_dense(self, it0, it1, seed, cstart, thinning, S, samples, fields, poll_every, s, max_launches):
-        """Dense mass: segments outside the middle windows run as they are; inside one, every
-        transition's draws (model space) join the window's pool, which persists across run()
-        calls (a kernel stepped one transition at a time pools the same draws), and the window's
-        last transition finalizes it and re-expresses every chain."""
+    def _run_window(self, plan, a, b, win):
+        """Dense mass, transitions [a, b) inside the middle window `win`: they run unthinned, in
+        chunks; every transition's draw (model space) joins the window's pool, which persists
+        across run() calls (a kernel stepped one transition at a time pools the same draws), the
+        draws the plan keeps are copied into their slots, and the window's last transition
+        finalizes the pool and re-expresses every chain."""
         from .dense import ChainWelford, PooledCovariance
         chunk = max(1, int(self.opts.dense_adapt_bytes) // (4 * self.D * self.ldc))
         wt = self.potential.whitening
         pos = self._positive()
+        s = plan.stream
+        if self._pool is None or self._pool[0] != win:
+            self._pool = (win, ChainWelford(self.D, self.C, self.device) if self.chain_dense
+                          else PooledCovariance(self.D, self.device, wt.mu))
+        pool = self._pool[1]
+        zbuf = torch.empty(self.D, self.ldc, dtype=torch.float32, device=self.device)
         launches = 0
-        for a, b, win in self._dense_segments(it0, it1):
-            if win is None:
-                # without mass adaptation the window ends still run the step-size search
-                cuts = self._search_cuts(a, b)
-                ends = sorted(set(cuts + [b]))
-                for p, q in zip([a] + ends[:-1], ends):
-                    if q > p:
-                        launches += self._run_segment(p, q, seed, cstart, thinning, S, samples, fields, poll_every,
-                                                      s, max_launches)
-                        self._convert_slots(samples, self._slots_in(p, q, cstart, thinning, S), s)
-                    if q in cuts:
-                        self._search_at_window_end(q, cstart, thinning, S, fields, s)
-                continue
-            if self._pool is None or self._pool[0] != win:
-                self._pool = (win, ChainWelford(self.D, self.C, self.device) if self.chain_dense
-                              else PooledCovariance(self.D, self.device, wt.mu))
-            pool = self._pool[1]
-            zbuf = torch.empty(self.D, self.ldc, dtype=torch.float32, device=self.device)
-            for ca in range(a, b, chunk):
-                cb = min(b, ca + chunk)
-                n = cb - ca
-                abuf = torch.empty((n, self.D, self.ldc), dtype=torch.float32, device=self.device)
-                afld = torch.zeros((n, len(native.COLLECT), self.ldc), dtype=torch.float32, device=self.device)
-                launches += self._run_segment(ca, cb, seed, ca, 1, n, abuf, afld, poll_every, s, max_launches)
-                for k in range(n):
-                    wt.to_model(abuf[k], zbuf, stream=s)
-                    if self.chain_dense:
-                        pool.add(zbuf, stream=s)
-                    else:
-                        pool.add(zbuf[:, :self.C])
-                    slot = self._slot_of(ca + k, cstart, thinning, S)
-                    if slot >= 0:
-                        if samples.shape[0] > 0:
-                            samples[slot].copy_(zbuf)
-                            if bool(pos.any()):
-                                samples[slot][pos] = torch.exp(samples[slot][pos])
-                        fields[slot].copy_(afld[k])
-                del abuf, afld
-            if b == win[1]:
+        for ca in range(a, b, chunk):
+            cb = min(b, ca + chunk)
+            n = cb - ca
+            every = replace(plan, cstart=ca, thinning=1, S=n,
+                            samples=torch.empty((n, self.D, self.ldc), dtype=torch.float32, device=self.device),
+                            fields=torch.zeros((n, len(native.COLLECT), self.ldc), dtype=torch.float32,
+                                               device=self.device))
+            launches += self._run_segment(every, ca, cb)
+            for k in range(n):
+                wt.to_model(every.samples[k], zbuf, stream=s)
                 if self.chain_dense:
-                    cov, mean = pool.finalize(self.opts.regularize_mass_matrix, self.blocks), None
+                    pool.add(zbuf, stream=s)
                 else:
-                    pool.all_reduce(self.device_group)
-                    cov, mean = pool.finalize(self.opts.regularize_mass_matrix)
-                self._pool = None
-                self._reexpress(cov, mean, s)
-                if self._heuristic():
-                    self._search_at_window_end(b, cstart, thinning, S, fields, s)
+                    pool.add(zbuf[:, :self.C])
+                slot = plan.slot_of(ca + k)
+                if slot >= 0:
+                    plan.put(slot, zbuf, pos)
+                    plan.fields[slot].copy_(every.fields[k])
+            del every
+        if b == win[1]:
+            if self.chain_dense:
+                cov, mean = pool.finalize(self.opts.regularize_mass_matrix, self.blocks), None
+            else:
+                pool.all_reduce(self.device_group)
+                cov, mean = pool.finalize(self.opts.regularize_mass_matrix)
+            self._pool = None
+            self._reexpress(cov, mean, s)
         return launches
 
     def _persistent_model(self):
@@ -629,82 +667,48 @@ class Engine:
         fn = getattr(self.potential, "wide_model", None)
         return fn() if fn is not None else None
 
-    def _run_segment(self, a, b, seed, cstart, thinning, S, samples, fields, poll_every, s, max_launches):
-        """Transitions [a, b) of every chain; collection slots per (cstart, thinning, S)."""
-        self._fill_cfg(a, b, self.num_warmup, seed, cstart, thinning, S)
-        cfgp = ctypes.byref(self.cfg)
-        arena = ptr(self.arena)
-        tr = self._collect_codes()
+    def _run_segment(self, plan, a, b):
+        """Transitions [a, b) of every chain, collected as the plan says, on the engine's
+        schedule: persistent wide, persistent small, or the launched loop."""
+        L, s = lib(), plan.stream
+        cfgp, arena = ctypes.byref(self.cfg), ptr(self.arena)
+        sp, fp, tp = plan.pointers()
         if self.persist_wide:
-            return self._run_wide_persistent(a, b, seed, cstart, thinning, S, samples, fields, s, max_launches)
-        check(lib().nmx_nuts_resume(cfgp, arena, s), "nmx_nuts_resume")
+            # nmx_nuts_run_wide: one launch runs every chain through the span.  The lockstep
+            # schedule (sync_chains) is one launch per transition: no chain starts transition
+            # t + 1 before every chain finished t, and each chain's computation is the same as
+            # unsynchronised
+            model, data, n = self.potential.wide_model()
+            spans = [(t, t + 1) for t in range(a, b)] if self.sync_chains else [(a, b)]
+            launches = 0
+            for t0, t1 in spans:
+                self._fill_cfg(t0, t1, plan)
+                self.cfg.sync_chains = 0
+                check(L.nmx_nuts_resume(cfgp, arena, s), "nmx_nuts_resume")
+                launches += self._until_done(t1 - t0, lambda m: check(
+                    L.nmx_nuts_run_wide(cfgp, arena, sp, fp, tp, model, ptr(data), n, m, s), "nmx_nuts_run_wide"))
+            return launches
+        self._fill_cfg(a, b, plan)
+        check(L.nmx_nuts_resume(cfgp, arena, s), "nmx_nuts_resume")
         small = self._persistent_model()
         if small is not None:
-            # one launch normally covers the segment (NUTS: <= 2^depth + 2 steps per
-            # transition); HMC trajectories (ceil(L / step) leapfrogs) may need more: the
-            # kernel resumes from the arena, so relaunch until every chain is DONE
             model, p0, p1, n = small
-            max_steps = (b - a) * ((1 << self.md) + 2) + 16
-            launches = 0
-            while True:
-                check(lib().nmx_nuts_run_small(cfgp, arena, ptr(samples) if samples.shape[0] else None, ptr(fields),
-                                               ptr(tr), model, ptr(p0),
-                                               ptr(p1), n, max_steps, s), "nmx_nuts_run_small")
-                launches += 1
-                if int(self.view("counters")[0].item()) >= self.C:
-                    return launches
-                if max_launches is not None and launches * max_steps >= max_launches:
-                    raise RuntimeError(f"chains did not finish within {max_launches} leapfrog steps")
-        groups = self._groups()
-        if groups > 1:
-            return self._run_groups(groups, samples, fields, tr, poll_every, s, max_launches)
-        done = self.view("counters")[0:1]
-        host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
-        ev = torch.cuda.Event()
-        pending = False
+            return self._until_done(b - a, lambda m: check(
+                L.nmx_nuts_run_small(cfgp, arena, sp, fp, tp, model, ptr(p0), ptr(p1), n, m, s), "nmx_nuts_run_small"))
+        return self._run_lanes(plan)
+
+    def _until_done(self, transitions, launch):
+        """The persistent schedules: launch(max_steps) until every chain is DONE; returns the
+        launches.  One launch normally covers the span (NUTS: <= 2^depth + 2 steps per
+        transition); HMC trajectories (ceil(L / step) leapfrogs) may hit the bound: the kernels
+        resume from the arena."""
+        max_steps = transitions * ((1 << self.md) + 2) + 16
         launches = 0
-        step = lib().nmx_nuts_step
-        sp, fp, tp = ptr(samples) if samples.shape[0] else None, ptr(fields), ptr(tr)
-        cfg = self.cfg
-        parity = 0
-        cfg.parity = parity
-        check(step(cfgp, arena, sp, fp, tp, s), "nmx_nuts_step")
-        evaluate = self.potential.evaluate
-        lists = self.eval_lists
-        for b in lists:
-            b.num_chains = self.C
-        wide = self._wide_model()
-        if wide is not None:
-            model, data, n = wide
-            if self._wide_ws is None:
-                nb = lib().nmx_nuts_wide_model_workspace_bytes(self.D, self.C)
-                self._wide_ws = torch.zeros(nb, dtype=torch.uint8, device=self.device)
-            wstep, dp, wsp = lib().nmx_nuts_step_wide_model, ptr(data), ptr(self._wide_ws)
         while True:
-            for _ in range(poll_every):
-                if wide is not None:
-                    check(wstep(cfgp, arena, sp, fp, tp, model, dp, n, wsp, s), "nmx_nuts_step_wide_model")
-                    continue
-                evaluate(lists[parity], s)
-                parity ^= 1
-                cfg.parity = parity
-                check(step(cfgp, arena, sp, fp, tp, s), "nmx_nuts_step")
-            launches += poll_every
-            if pending:
-                ev.synchronize()
-                done_n = int(host[0])
-                if done_n >= self.C:
-                    break
-                # finished chains never re-enter the lists: C - done bounds every later list
-                # count, and kernels size their grids by it (nmx_eval_batch.num_chains)
-                for b in lists:
-                    b.num_chains = self.C - done_n
-            host.copy_(done, non_blocking=True)
-            ev.record()
-            pending = True
-            if max_launches is not None and launches >= max_launches:
-                raise RuntimeError(f"chains did not finish within {max_launches} leapfrog launches")
-        return launches
+            launch(max_steps)
+            launches += 1
+            if int(self.view("counters")[0].item()) >= self.C:
+                return launches
 
     def _groups(self):
         """Chain groups of the launched fused step (1: none): dim <= 256 models whose potential
@@ -719,100 +723,102 @@ class Engine:
             return 1
         return G
 
-    def _run_groups(self, G, samples, fields, tr, poll_every, s, max_launches):
-        """The launched loop with chain groups (nmx_nuts_config.num_groups): group g's potential
-        and step launches go to stream g (the caller's stream for g = 0), each group with its
-        own compacted lists and DONE count, so a group's latency-bound step, finalize and run
-        tail overlap the other groups' potential.  A chain's computation does not depend on its
-        group: draws are bitwise those of the one-stream loop."""
+    def _lanes(self, plan):
+        """The lanes of the launched loop, each after its first step.  One stream is one lane:
+        self.cfg, the arena's two lists and the DONE count of all chains, on the caller's
+        stream; for a D-split model with a fused step (_wide_model) its advance is that one
+        call, which has no potential launch and no parity.  Chain groups
+        (nmx_nuts_config.num_groups) are G lanes: group g's potential and step launches go to
+        stream g (the caller's stream for g = 0), each group with its own compacted lists and
+        DONE count, so a group's latency-bound step, finalize and run tail overlap the other
+        groups' potential.  A chain's computation does not depend on its group: draws are
+        bitwise those of the one-stream loop."""
+        L, s, G = lib(), plan.stream, self._groups()
+        arena = ptr(self.arena)
+        sp, fp, tp = plan.pointers()
+        evaluate, counters = self.potential.evaluate, self.view("counters")
+
+        def lane(cfg, lists, raw, stream, done, size, *slot):
+            cfgp = ctypes.byref(cfg)
+            cfg.parity = 0
+            check(L.nmx_nuts_step(cfgp, arena, sp, fp, tp, raw), "nmx_nuts_step")
+
+            def advance():
+                evaluate(lists[cfg.parity], raw, *slot)
+                cfg.parity ^= 1
+                check(L.nmx_nuts_step(cfgp, arena, sp, fp, tp, raw), "nmx_nuts_step")
+
+            return Lane(cfg, lists, stream, done, size, advance, live=size > 0)
+
+        if G == 1:
+            for b in self.eval_lists:
+                b.num_chains = self.C
+            one = lane(self.cfg, self.eval_lists, s, None, counters[0:1], self.C)
+            wide = self._wide_model()
+            if wide is not None:  # D-split models only: they never run in groups (_groups)
+                model, data, n = wide
+                if self._wide_ws is None:
+                    nb = L.nmx_nuts_wide_model_workspace_bytes(self.D, self.C)
+                    self._wide_ws = torch.zeros(nb, dtype=torch.uint8, device=self.device)
+                cfgp, dp, wsp = ctypes.byref(self.cfg), ptr(data), ptr(self._wide_ws)
+                one.advance = lambda: check(
+                    L.nmx_nuts_step_wide_model(cfgp, arena, sp, fp, tp, model, dp, n, wsp, s), "nmx_nuts_step_wide_model")
+            return [one]
         main = torch.cuda.ExternalStream(s, device=self.device)
         while len(self._side_streams) < G - 1:
             self._side_streams.append(torch.cuda.Stream(device=self.device))
         streams = [main] + self._side_streams[:G - 1]
-        raw = [s] + [int(st.cuda_stream) for st in streams[1:]]
         start = torch.cuda.Event()
         start.record(main)
         for st in streams[1:]:
             st.wait_event(start)  # after the resume / setup issued on the caller's stream
         gsz = (self.C + G - 1) // G
-        sizes = [max(0, min(gsz, self.C - g * gsz)) for g in range(G)]
-        step = lib().nmx_nuts_step
-        arena = ptr(self.arena)
-        sp, fp, tp = ptr(samples) if samples.shape[0] else None, ptr(fields), ptr(tr)
-        idx, cnt = ptr(self.view("active_idx")), ptr(self.view("counters"))
+        idx, cnt = ptr(self.view("active_idx")), ptr(counters)
         z, gr, pe, ph = (ptr(self.view(n)) for n in ("z_eval", "g_eval", "pe_eval", "phase"))
-        counters = self.view("counters")
-        cfgs, lists, par = [], [], [0] * G
-        for g in range(G):
+        lanes = []
+        for g, st in enumerate(streams):
+            size = max(0, min(gsz, self.C - g * gsz))
             c = NutsConfig.from_buffer_copy(self.cfg)
-            c.num_groups, c.group, c.parity = G, g, 0
-            cfgs.append(c)
-            lists.append([EvalBatch(z=z, grad=gr, pe=pe, phase=ph, active_idx=idx + 4 * (p * self.ldc + g * gsz),
-                                    active_count=cnt + 4 * (2 + 2 * g + p), num_chains=max(sizes[g], 1),
-                                    ldc=self.ldc) for p in (0, 1)])
-            check(step(ctypes.byref(c), arena, sp, fp, tp, raw[g]), "nmx_nuts_step")
-        evaluate = self.potential.evaluate
-        hosts = [torch.zeros(1, dtype=torch.int32, pin_memory=True) for _ in range(G)]
-        evs = [torch.cuda.Event() for _ in range(G)]
-        pending, live = [False] * G, [sizes[g] > 0 for g in range(G)]
-        launches = 0
-        while any(live):
-            for _ in range(poll_every):
-                for g in range(G):
-                    if not live[g]:
-                        continue
-                    evaluate(lists[g][par[g]], raw[g], g)
-                    par[g] ^= 1
-                    cfgs[g].parity = par[g]
-                    check(step(ctypes.byref(cfgs[g]), arena, sp, fp, tp, raw[g]), "nmx_nuts_step")
-            launches += poll_every
-            for g in range(G):
-                if not live[g]:
-                    continue
-                if pending[g]:
-                    evs[g].synchronize()
-                    done_g = int(hosts[g][0])
-                    if done_g >= sizes[g]:
-                        live[g] = False
-                        continue
-                    for b in lists[g]:  # finished chains never re-enter the group's lists
-                        b.num_chains = sizes[g] - done_g
-                with torch.cuda.stream(streams[g]):
-                    hosts[g].copy_(counters[10 + g:11 + g], non_blocking=True)
-                    evs[g].record(streams[g])
-                pending[g] = True
-            if max_launches is not None and launches >= max_launches:
-                raise RuntimeError(f"chains did not finish within {max_launches} leapfrog launches")
-        for st in streams[1:]:  # the caller's stream continues after every group's work
-            j = torch.cuda.Event()
-            j.record(st)
-            main.wait_event(j)
-        return launches
+            c.num_groups, c.group = G, g
+            lists = [EvalBatch(z=z, grad=gr, pe=pe, phase=ph, active_idx=idx + 4 * (p * self.ldc + g * gsz),
+                               active_count=cnt + 4 * (2 + 2 * g + p), num_chains=max(size, 1), ldc=self.ldc)
+                     for p in (0, 1)]
+            lanes.append(lane(c, lists, s if g == 0 else int(st.cuda_stream), st, counters[10 + g:11 + g], size, g))
+        return lanes
 
-    def _run_wide_persistent(self, a, b, seed, cstart, thinning, S, samples, fields, s, max_launches):
-        """nmx_nuts_run_wide: one launch runs every chain through [a, b) (relaunched while
-        some chain hit the leaf bound, e.g. long HMC trajectories).  The lockstep schedule
-        (sync_chains) is one launch per transition: no chain starts transition t + 1 before
-        every chain finished t, and each chain's computation is the same as unsynchronised."""
-        model, data, n = self.potential.wide_model()
-        tr = self._collect_codes()
-        sp, fp, tp, dp = ptr(samples) if samples.shape[0] else None, ptr(fields), ptr(tr), ptr(data)
-        run = lib().nmx_nuts_run_wide
-        spans = [(t, t + 1) for t in range(a, b)] if self.sync_chains else [(a, b)]
+    def _run_lanes(self, plan):
+        """The launched loop  nuts_step -> [potential -> nuts_step] * n  of every lane, until
+        every chain is DONE; returns the launches per lane."""
+        lanes = self._lanes(plan)
         launches = 0
-        for t0, t1 in spans:
-            self._fill_cfg(t0, t1, self.num_warmup, seed, cstart, thinning, S)
-            self.cfg.sync_chains = 0
-            cfgp = ctypes.byref(self.cfg)
-            check(lib().nmx_nuts_resume(cfgp, ptr(self.arena), s), "nmx_nuts_resume")
-            max_steps = (t1 - t0) * ((1 << self.md) + 2) + 16
-            while True:
-                check(run(cfgp, ptr(self.arena), sp, fp, tp, model, dp, n, max_steps, s), "nmx_nuts_run_wide")
-                launches += 1
-                if int(self.view("counters")[0].item()) >= self.C:
-                    break
-                if max_launches is not None and launches * max_steps >= max_launches:
-                    raise RuntimeError(f"chains did not finish within {max_launches} leapfrog steps")
+        while any(ln.live for ln in lanes):
+            for _ in range(plan.poll_every):
+                for ln in lanes:
+                    if ln.live:
+                        ln.advance()
+            launches += plan.poll_every
+            for ln in lanes:
+                if not ln.live:
+                    continue
+                if ln.pending:
+                    ln.event.synchronize()
+                    done = int(ln.host[0])
+                    if done >= ln.size:
+                        ln.live = False
+                        continue
+                    # finished chains never re-enter the lane's lists: size - done bounds every
+                    # later list count, and kernels size their grids by it
+                    # (nmx_eval_batch.num_chains)
+                    for b in ln.lists:
+                        b.num_chains = ln.size - done
+                with torch.cuda.stream(ln.stream):  # None: the current stream
+                    ln.host.copy_(ln.done, non_blocking=True)
+                    ln.event.record(ln.stream)
+                ln.pending = True
+        for ln in lanes[1:]:  # the caller's stream continues after every group's work
+            j = torch.cuda.Event()
+            j.record(ln.stream)
+            lanes[0].stream.wait_event(j)
         return launches
 
     def _grow_finished(self, n):

@@ -200,6 +200,16 @@ def _flatten_init(pot, init_params, num_chains):
     return pot.flatten(init_params) if isinstance(init_params, dict) else init_params
 
 
+def init_rows(pot, init_params, num_chains):
+    """init_params -> the float32 rows of `num_chains` chains, one per chain (a [D] value is every
+    chain's start).  `pot` is the model's potential (Engine.model_potential, not a whitening
+    wrapper around it)."""
+    import torch
+
+    ip = torch.as_tensor(_flatten_init(pot, init_params, num_chains), dtype=torch.float32)
+    return ip[None, :].expand(num_chains, -1) if ip.dim() == 1 else ip
+
+
 class HMC(MCMCKernel):
     """Hamiltonian Monte Carlo with fixed trajectory length (numpyro/infer/hmc.py:541-822)."""
 
@@ -387,12 +397,7 @@ class HMC(MCMCKernel):
         self.bind_potential_fn(init_params, int(num_chains))
         eng = self.make_engine(int(num_chains), model_args, model_kwargs, device=device,
                                chain_offset=chain_offset)
-        ip = None
-        if init_params is not None:
-            ip = _flatten_init(eng.model_potential, init_params, int(num_chains))
-            ip = torch.as_tensor(ip, dtype=torch.float32)
-            if ip.dim() == 1:
-                ip = ip[None, :].expand(eng.C, -1)
+        ip = None if init_params is None else init_rows(eng.model_potential, init_params, int(num_chains))
         with torch.cuda.device(eng.device):
             eng.initialize(seed, int(num_warmup), init_params=ip, radius=self.init_radius())
         self._engine, self._seed = eng, seed

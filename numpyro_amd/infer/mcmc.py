@@ -12,12 +12,15 @@ guarantees the same up to its stream, test/infer/test_mcmc.py:553-592).  Under
 """
 from __future__ import annotations
 
+import time
+import warnings
+
 import numpy as np
 import torch
 
 from .. import diagnostics, native, shard
 from ..random import key_to_seed
-from .hmc import restore_state, snapshot_state
+from .hmc import _args_key, init_rows, restore_state, snapshot_state
 
 _FIELD_ALIASES = {"adapt_state.step_size": "step_size", "i": "i"}
 # HMCState fields (hmc.py:31-48) the device does not collect per transition but that follow from
@@ -52,8 +55,6 @@ def _postprocess_per_draw(fn, sites):
     in chunks of _VMAP_CHUNK draws, or -- only when vmap cannot batch fn (e.g. it converts to
     Python numbers) -- one call per draw, with a warning (8192 chains x 1000 draws is 8M calls).
     Any other error of fn propagates.  sites: {site: [C, S, *shape]} -> {name: [C, S, *out_shape]}."""
-    import warnings
-
     v0 = next(iter(sites.values()))
     C, S = int(v0.shape[0]), int(v0.shape[1])
     n = C * S
@@ -126,14 +127,24 @@ class MCMC:
         self._samples = None
         self._fields = None
         self._collected = ()
+        self._derived = ()  # the _DERIVED_FIELDS of the last run, and their values once asked for
+        self._derived_cache = {}
+        self._host_constrain = False  # the last run's draws are unconstrained, for z_grad
+        self._fields_only = False  # runs collect the extra fields only, no draws
         self._args, self._kwargs = (), {}
         self._host_potential = None  # (args key, potential) for results of an unpickled MCMC
         self.last_run_stats = {}
 
     # ------------------------------------------------------------------ engine
+    def _cache_key(self, args, kwargs, devs=()):
+        """What the cached engines are bound to.  A callable potential_fn is re-bound when
+        init_params change structure (bind_potential_fn): the engines of the old potential, and
+        its dimension, go with it."""
+        return (id(self.sampler), _args_key(args, kwargs), tuple(str(d) for d in devs),
+                id(getattr(self.sampler, "_potential", None)) if getattr(self.sampler, "_potential_fn", None) else 0)
+
     def _get_engine(self, args, kwargs):
-        key = (id(self.sampler), tuple(id(a) for a in args), tuple(sorted((k, id(v)) for k, v in kwargs.items())),
-               id(getattr(self.sampler, "_potential", None)) if getattr(self.sampler, "_potential_fn", None) else 0)
+        key = self._cache_key(args, kwargs)
         if self._engine is None or self._engine_key != key:
             dev = self.device if self.device is not None or not self.devices else self.devices[0]
             self._engine = self.sampler.make_engine(self.local_chains, args, kwargs, device=dev,
@@ -164,12 +175,7 @@ class MCMC:
     def _get_engines(self, args, kwargs, devs):
         import pickle
 
-        from .hmc import _args_key
-
-        # a callable potential_fn is re-bound when init_params change structure (bind_potential_fn):
-        # the engines of the old potential, and its dimension, go with it -- as in _get_engine
-        key = (id(self.sampler), _args_key(args, kwargs), tuple(str(d) for d in devs),
-               id(getattr(self.sampler, "_potential", None)) if getattr(self.sampler, "_potential_fn", None) else 0)
+        key = self._cache_key(args, kwargs, devs)
         if self._engines is None or self._engine_key != key:
             engines = []
             pot_fn = getattr(self.sampler, "_potential_fn", None)
@@ -212,12 +218,6 @@ class MCMC:
     def last_state(self):
         return self._last_state
 
-    def _snapshot(self, eng, seed):
-        return snapshot_state(eng, seed, keep_arena=True)
-
-    def _restore(self, eng, state):
-        restore_state(eng, state)
-
     # ------------------------------------------------------------------ run
     def warmup(self, rng_key, *args, extra_fields=(), collect_warmup=False, init_params=None, **kwargs):
         self._warmup_state = None
@@ -234,15 +234,13 @@ class MCMC:
                       n_iter=self.num_warmup + self.num_samples, lower=self.num_warmup)
 
     def _init_rows(self, pot, init_params):
-        """init_params -> the [local_chains, D] float32 rows of this process's chains.  `pot` is the
-        model's potential (Engine.model_potential, not a whitening wrapper around it).  All
-        num_chains chains are flattened -- a [D] value is every chain's start -- and a process
-        that holds a shard of them (torch.distributed) keeps rows [chain_lo, chain_hi)."""
-        from .hmc import _flatten_init
-
-        ip = torch.as_tensor(_flatten_init(pot, init_params, self.num_chains), dtype=torch.float32)
-        if ip.dim() == 1:
-            ip = ip[None, :].expand(self.num_chains, -1)
+        """init_params -> the [local_chains, D] float32 rows of this process's chains (None: none
+        given).  `pot` is the model's potential (Engine.model_potential, not a whitening wrapper
+        around it).  All num_chains chains are flattened -- a [D] value is every chain's start --
+        and a process that holds a shard of them (torch.distributed) keeps rows [chain_lo, chain_hi)."""
+        if init_params is None:
+            return None
+        ip = init_rows(pot, init_params, self.num_chains)
         if ip.shape[0] == self.num_chains and self.local_chains != self.num_chains:
             ip = ip[self.chain_lo:self.chain_hi]
         if ip.dim() != 2 or ip.shape[0] != self.local_chains:
@@ -282,44 +280,49 @@ class MCMC:
             # reference's rule: batched when num_chains > 1), not this process's shard of it
             bind(init_params, self.num_chains)
         devs = self._run_devices()
+        engines = [self._get_engine(args, kwargs)] if devs is None else self._get_engines(args, kwargs, devs)
+        self._args, self._kwargs = tuple(args), dict(kwargs)
+        eng = engines[0]
+        ip = self._init_rows(eng.model_potential, init_params if resume is None else None)
         if devs is not None:
-            return self._run_multi(devs, seed, args, kwargs, init_params, n_iter, lower, resume)
-        eng = self._get_engine(args, kwargs)
-        self._args, self._kwargs = tuple(args), dict(kwargs)
+            return self._run_multi(engines, seed, ip, n_iter, lower, resume)
+        self._samples, self._fields, launches, ms, self._last_state = self._run_engine(
+            eng, seed, n_iter, lower, resume, ip, device_events=True)
+        self.last_run_stats = {"launches": launches, "device_ms": ms, "iterations": n_iter}
+
+    def _run_engine(self, eng, seed, n_iter, lower, resume, ip, device_events):
+        """One engine's share of a run: restore `resume` or initialize (from the rows `ip`, if
+        any), run and snapshot; returns (samples, fields, launches, ms, state).  The time is
+        that of eng.run: between device events for a single engine, on the host clock up to a
+        synchronize for a device thread of a multi-device run."""
         eng.constrain_samples = self.postprocess_fn is None and not self._host_constrain
-        dev = eng.device
-        with torch.cuda.device(dev):
+        with torch.cuda.device(eng.device):
             if resume is not None:
-                self._restore(eng, resume)
+                restore_state(eng, resume)
             else:
-                ip = None if init_params is None else self._init_rows(eng.model_potential, init_params)
                 eng.initialize(seed, self.num_warmup, init_params=ip, radius=self.sampler.init_radius())
-            start = torch.cuda.Event(enable_timing=True)
-            end = torch.cuda.Event(enable_timing=True)
-            start.record()
+            if device_events:
+                start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                start.record()
+            t0 = time.perf_counter()
             samples, fields, launches = eng.run(n_iter, seed, collect_begin=lower, thinning=self.thinning,
-                                                poll_every=self.poll_every,
-                                                collect_samples=not getattr(self, "_fields_only", False))
-            end.record()
-            end.synchronize()
-            self.last_run_stats = {"launches": launches, "device_ms": start.elapsed_time(end),
-                                   "iterations": n_iter}
-        self._samples, self._fields = samples, fields
-        self._last_state = self._snapshot(eng, seed)
+                                                poll_every=self.poll_every, collect_samples=not self._fields_only)
+            if device_events:
+                end.record()
+                end.synchronize()
+                ms = start.elapsed_time(end)
+            else:
+                torch.cuda.synchronize(eng.device)
+                ms = (time.perf_counter() - t0) * 1e3
+            return samples, fields, launches, ms, snapshot_state(eng, seed, keep_arena=True)
 
-    def _run_multi(self, devs, seed, args, kwargs, init_params, n_iter, lower, resume):
-        """The chains sharded over `devs` (contiguous global chain ids, like the torchrun ranks),
-        each shard's engine driven by its own host thread (the library calls release the GIL),
-        draws and fields gathered to the first device in global chain order."""
+    def _run_multi(self, engines, seed, ip_all, n_iter, lower, resume):
+        """The chains sharded over the devices of `engines` (contiguous global chain ids, like the
+        torchrun ranks), each shard's engine driven by its own host thread (the library calls
+        release the GIL), draws and fields gathered to the first device in global chain order."""
         import threading
-        import time
 
-        engines = self._get_engines(args, kwargs, devs)
-        self._args, self._kwargs = tuple(args), dict(kwargs)
         G = len(engines)
-        ip_all = None
-        if resume is None and init_params is not None:
-            ip_all = self._init_rows(engines[0].model_potential, init_params)
         parts = None
         if resume is not None:
             parts = getattr(resume, "_parts", None)
@@ -332,23 +335,11 @@ class MCMC:
         def work(g):
             eng = engines[g]
             try:
-                eng.constrain_samples = self.postprocess_fn is None and not self._host_constrain
-                with torch.cuda.device(eng.device):
-                    if parts is not None:
-                        self._restore(eng, parts[g])
-                    else:
-                        ip = None
-                        if ip_all is not None:
-                            lo, hi = shard_chains(self.local_chains, g, G)
-                            ip = ip_all[lo:hi]
-                        eng.initialize(seed, self.num_warmup, init_params=ip, radius=self.sampler.init_radius())
-                    t0 = time.perf_counter()
-                    samples, fields, launches = eng.run(n_iter, seed, collect_begin=lower, thinning=self.thinning,
-                                                        poll_every=self.poll_every,
-                                                        collect_samples=not getattr(self, "_fields_only", False))
-                    torch.cuda.synchronize(eng.device)
-                    out[g] = (samples[:, :, :eng.C], fields[:, :, :eng.C], launches,
-                              (time.perf_counter() - t0) * 1e3, self._snapshot(eng, seed))
+                lo, hi = shard_chains(self.local_chains, g, G)
+                samples, fields, *rest = self._run_engine(
+                    eng, seed, n_iter, lower, None if parts is None else parts[g],
+                    None if ip_all is None else ip_all[lo:hi], device_events=False)
+                out[g] = (samples[:, :, :eng.C], fields[:, :, :eng.C], *rest)
             except BaseException as e:  # noqa: BLE001  (re-raised below; the others must not wait)
                 errs.append(e)
                 group.abort()
@@ -395,7 +386,7 @@ class MCMC:
         else:
             # the device collection has applied exp, unless the draws were kept unconstrained for
             # z_grad; the sigmoid / lower-bound sites are always completed here
-            out = pot.constrain(out, device_exp=not getattr(self, "_host_constrain", False))
+            out = pot.constrain(out, device_exp=not self._host_constrain)
             if include_deterministic:
                 out.update(pot.deterministic(out))
         if not group_by_chain:
@@ -421,7 +412,7 @@ class MCMC:
             if not group_by_chain:
                 v = v.reshape(-1)
             out["adapt_state.step_size" if f == "step_size" else f] = v
-        for f in getattr(self, "_derived", ()):
+        for f in self._derived:
             out[f] = self._derived_field(f, group_by_chain)
         return out
 
@@ -512,6 +503,10 @@ class MCMC:
         state["_engines"] = None
         state["_host_potential"] = None
         return state
+
+    def __setstate__(self, state):
+        # a pickle of an earlier version may lack the attributes it set only during a run
+        self.__dict__.update(dict(_derived=(), _derived_cache={}, _host_constrain=False, _fields_only=False), **state)
 
 
 def _combine_states(parts, engines, device):

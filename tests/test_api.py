@@ -121,6 +121,54 @@ def test_dense_segments_split_at_middle_window_ends():
     assert Engine._dense_segments(Fake(), 0, 2000) == [(0, 2000, None)]
 
 
+@pytest.mark.parametrize("W", [0, 19, 40, 150, 1000])
+def test_segment_plan_covers_the_run_and_marks_windows_and_searches(W):
+    """Engine._segments, the one list run() walks in both mass modes, against the middle windows of
+    the oracle's schedule: the segments cover [it0, it1) once and in order; with dense adaptation a
+    segment lies in a middle window exactly when it carries that window; a search is marked at
+    exactly the middle-window ends e with it0 < e <= it1 when the heuristic is on."""
+    import itertools
+
+    from numpyro_amd.engine import SamplerOptions
+
+    middle = [(a, b + 1) for a, b in H.build_adaptation_schedule(W)[1:-1]]
+    assert bool(middle) == (W >= 20)
+    runs = [(0, W + 50)]
+    if middle:
+        ws, we = middle[len(middle) // 2]
+        inside = (ws + we) // 2
+        assert ws < inside < we
+        runs += [(inside, W + 50), (0, inside)]  # starts inside a middle window, ends inside one
+    for dense, adapt, search in itertools.product((False, True), repeat=3):
+        eng = object.__new__(Engine)
+        eng.num_warmup, eng.dense = W, dense
+        eng.opts = SamplerOptions(dense_mass=dense, adapt_mass_matrix=adapt, find_heuristic_step_size=search)
+        for it0, it1 in runs:
+            segs = eng._segments(it0, it1)
+            label = (W, dense, adapt, search, it0, it1, segs)
+            assert segs[0][0] == it0 and segs[-1][1] == it1, label
+            assert all(a < b for a, b, _, _ in segs), label
+            assert all(p[1] == q[0] for p, q in zip(segs, segs[1:])), label
+            for a, b, win, _ in segs:
+                holding = [w for w in middle if w[0] <= a and b <= w[1]]
+                if dense and adapt:
+                    assert win == (holding[0] if holding else None), label
+                    assert holding or all(b <= w[0] or w[1] <= a for w in middle), label
+                else:
+                    assert win is None, label
+            want = {e for _, e in middle if it0 < e <= it1} if search else set()
+            assert {b for _, b, _, at_b in segs if at_b} == want, label
+    if W == 1000:
+        # the expectations above agree with what test_dense_segments_split_at_middle_window_ends
+        # asserts of _dense_segments, whose segments the plan takes over unchanged without a search
+        eng.opts = SamplerOptions(dense_mass=True, adapt_mass_matrix=True)
+        whole = [s[:3] for s in eng._segments(0, 2000)]
+        assert whole == eng._dense_segments(0, 2000)
+        assert [(a, b) for a, b, w in whole if w] == middle and all(w == (a, b) for a, b, w in whole if w)
+        assert whole[0] == (0, 75, None) and whole[-1] == (950, 2000, None)
+        assert [s[:3] for s in eng._segments(80, 120)] == [(80, 100, (75, 100)), (100, 120, (100, 150))]
+
+
 def test_host_diagnostics_known_values():
     rs = np.random.RandomState(0)
     iid = rs.randn(4, 4000)

@@ -5,7 +5,7 @@ unthinned run of the same seed bitwise on the rows fori_collect keeps: for n tra
 start + k - 1 :: k with start = n % k (numpyro/util.py:330-346).  The device reads
 collect_thinning in tree_phase (csrc/nuts.hip: the slot off / thin, written when off % thin ==
 thin - 1) once per kernel family -- one row of tests/ending_cases.py's schedule table each -- and the
-dense path has a host twin (Engine._run_dense copies the slots of a middle window,
+dense path has a host twin (Engine._run_window copies the slots of a middle window,
 _convert_slots maps the others to model space, _search_at_window_end rewrites a slot's step
 size).  The expected rows are indexed out of the unthinned arrays here, not by Engine._slot_of
 (the code under test).  Every site and every collected field is compared with assert_array_equal."""
@@ -99,22 +99,33 @@ def test_thinned_run_keeps_the_unthinned_rows(device, row, thinning, monkeypatch
     assert full_w["num_steps"].max() > 1 and np.ptp(full_w["adapt_state.step_size"]) > 0
 
 
-@pytest.mark.parametrize("dense_mass", [True, "pooled"])
-def test_thinned_dense_adaptation_keeps_the_unthinned_rows(device, dense_mass):
+@pytest.mark.parametrize("dense_mass, k, search", [
+    pytest.param(True, 3, False, id="True"), pytest.param("pooled", 3, False, id="pooled"),
+    pytest.param(True, 4, True, id="True-search-thinning4")])
+def test_thinned_dense_adaptation_keeps_the_unthinned_rows(device, dense_mass, k, search):
     """Eight schools with an adapted dense mass (per chain, pooled): 40 warmup transitions have one
-    middle window (6 to 35), inside which Engine._run_dense runs unthinned and copies the kept
-    slots on the host; outside it _convert_slots maps the kept slots to model space."""
-    W, S, k = 40, 7, 3
+    middle window (6 to 35), inside which Engine._run_window runs unthinned and copies the kept
+    slots on the host; outside it _convert_slots maps the kept slots to model space.  With
+    find_heuristic_step_size at thinning 4 the kept rows 3, 7, ..., 39 hold row 35, the window's
+    last transition: its slot, copied on the host, is then rewritten by the step-size search
+    (Engine._search_at_window_end)."""
+    W, S = 40, 7
     sched = H.build_adaptation_schedule(W)
     assert [tuple(w) for w in sched[1:-1]] == [(6, 35)]
     rows = kept(W, k)
     assert np.sum((rows >= 6) & (rows <= 35)) >= 3 and np.sum(rows < 6) >= 1 and np.sum(rows > 35) >= 1
+    kw = dict(dense_mass=dense_mass, find_heuristic_step_size=True) if search else dict(dense_mass=dense_mass)
     args = (8, datasets.EIGHT_SCHOOLS_SIGMA, datasets.EIGHT_SCHOOLS_Y)
-    full_w, full_s = _full(("eight", dense_mass), P.eight_schools, args, W, S, dense_mass=dense_mass)
-    warm, samp, eng = _both_phases(P.eight_schools, args, W, S, k, dense_mass=dense_mass)
+    full_w, full_s = _full(("eight", dense_mass, search), P.eight_schools, args, W, S, **kw)
+    warm, samp, eng = _both_phases(P.eight_schools, args, W, S, k, **kw)
     assert eng.dense and eng.chain_dense == (dense_mass is True)
     _assert_thinned(f"eight schools dense_mass={dense_mass} warmup", full_w, warm, W, k)
     _assert_thinned(f"eight schools dense_mass={dense_mass} run", full_s, samp, S, k)
+    if search:
+        assert rows.tolist() == list(range(3, 40, 4)) and 35 in rows
+        # the searched step is what the window's last transition reports
+        step = full_w["adapt_state.step_size"]
+        assert np.any(step[:, 35] != step[:, 34])
 
 
 def test_thinned_step_size_search_rewrites_the_kept_slot(device, monkeypatch):

@@ -169,6 +169,41 @@ def test_device_engines_follow_a_rebound_potential_fn(recording):
         mcmc.run(0, init_params=torch.arange(8.0).reshape(4, 2))
     assert sorted((e.chain_offset, e.D, e.start.tolist()) for e in recording.log) == \
         [(0, 2, [[0.0, 1.0], [2.0, 3.0]]), (2, 2, [[4.0, 5.0], [6.0, 7.0]])]
+    # one run path: the device engines start from the [lo:hi] slices of the rows that a single
+    # engine is handed for the same init_params, and HMC.init hands its engine those rows too
+    for ip in (torch.arange(8.0).reshape(4, 2), {"x": torch.arange(8.0).reshape(4, 2)}):
+        single = MCMC(NUTS(potential_fn=quad), num_warmup=0, num_samples=1, num_chains=4, progress_bar=False)
+        one = _start(single, ip).start
+        assert one.shape == (4, 2) and one.dtype == torch.float32
+        recording.log.clear()
+        with pytest.raises(Started):
+            mcmc.run(0, init_params=ip)
+        shards = {e.chain_offset: e.start for e in recording.log}
+        assert sorted(shards) == [0, 2] and all(torch.equal(shards[lo], one[lo:lo + 2]) for lo in shards)
+        kernel = NUTS(potential_fn=quad)
+        with pytest.raises(Started):
+            kernel.init(0, 0, init_params=ip, num_chains=4)
+        assert torch.equal(recording.log[-1].start, one)
+
+
+def test_parallel_chains_without_devices_advise_once(recording, monkeypatch):
+    """The default chain_method="parallel" with several local chains, several visible GPUs and no
+    devices=: one engine, and the advice to pass devices='all', once per process."""
+    import warnings
+
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "device_count", lambda: 2)
+    monkeypatch.setattr(MCMC, "_warned_devices", False, raising=False)
+    mcmc = MCMC(NUTS(potential_fn=quad), num_warmup=0, num_samples=1, num_chains=2, progress_bar=False)
+    assert mcmc.chain_method == "parallel" and mcmc.devices is None
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        assert mcmc._run_devices() is None
+    assert [w.category for w in caught] == [UserWarning] and "devices='all'" in str(caught[0].message)
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        assert mcmc._run_devices() is None
+    assert caught == []
 
 
 def test_init_radius():
