@@ -475,6 +475,30 @@ int nmx_logreg_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_ev
  * do not depend on how many chains or GPUs share the work). */
 int nmx_logreg_num_splits(int64_t n_rows);
 
+/* Softmax (multinomial logistic) regression: coefs ~ N(0,1)^(D x K),
+ * obs ~ Categorical(logits = X @ coefs), coordinate of coefs[d][k] = d K + k (ravel order):
+ *   U(W)  = sum_n [logsumexp_k l_nk - l_{n, y_n}] + sum_dk [W_dk^2 / 2 + log(2 pi) / 2],  l = X W
+ *   dU/dW = X^T (softmax(l) - onehot(y)) + W
+ * 1 <= dim <= 64, 2 <= num_classes <= 32, n_rows >= 1; anything else is NMX_ERR_INVALID with the
+ * number named, before any launch.  X [n_rows][dim] float and the int32 labels are first packed
+ * (split-bf16 MFMA fragments per 32-row tile with the labels as class indices, and the float64
+ * table S[d][k] = sum_{n: y_n = k} X[n][d] of U's linear part); nmx_softmax_pack synchronises the
+ * stream once and fails, naming the first such row, on a label outside [0, num_classes).  Per
+ * tile the kernel runs two split-bf16 MFMA GEMMs (X.W and X^T.(softmax - onehot)) with a
+ * cross-lane softmax on the accumulator registers between them (a column tile is 32 / KP chains
+ * x KP classes, KP the power of two >= num_classes); per-split partial slabs, then a fixed-order
+ * reduction.  The number of row splits depends on n_rows only, so a chain's results are bitwise
+ * independent of the chains sharing the launch.  Honours phase / active_idx / num_chains < ldc
+ * like the other fused kernels.  The workspace holds slabs of ldc columns:
+ * nmx_softmax_workspace_bytes sizes it for ldc = num_chains rounded up to 64, so a caller whose
+ * arena is wider passes its ldc there. */
+size_t nmx_softmax_packed_bytes(int64_t n_rows, int dim, int num_classes);
+int nmx_softmax_pack(const float* X, const int32_t* y, int64_t n_rows, int dim, int num_classes, void* packed,
+                     void* stream);
+size_t nmx_softmax_workspace_bytes(int64_t n_rows, int dim, int num_classes, int num_chains);
+int nmx_softmax_pe_grad(const void* packed, int64_t n_rows, int dim, int num_classes, const nmx_eval_batch* ev,
+                        void* workspace, void* stream);
+
 /* ---- dense mass matrix (hmc_util.py:1203-1220 dense matvecs, hmc.py:103-108 momentum,
  *      hmc_util.py:612-620 dense Welford finalize) ----
  * With inverse mass M^-1 = T T^T, NUTS with dense mass on z is NUTS with identity mass on

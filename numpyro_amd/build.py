@@ -42,7 +42,8 @@ COMMON_FLAGS = [
 # per-file flags:
 # * the covtype kernel's epilogue and residual split stay scalar VALU (the SLP vectorizer would
 #   pair them into v_pk_*_f32, which issue slower beside MFMAs on gfx950; potential_logreg.hip
-#   x3_epi_one);
+#   x3_epi_one); the softmax-regression kernel's epilogue likewise, and with the packed f32
+#   operations switched off for the file, so no other pass forms them either;
 # * no floating-point contraction in the step kernels, the small models' potentials and the
 #   program potential and predictive program (bodies in a header, nmx_program.h, like the small
 #   models; the predictive draws' accept tests round like their NumPy restatement, and so do the
@@ -54,6 +55,8 @@ COMMON_FLAGS = [
 #   depends on each kernel's code generation -- with contraction off every kernel rounds every
 #   product, so the schedules stay bitwise identical (and round like the NumPy oracle)
 FILE_FLAGS = {"potential_logreg.hip": ["-fno-slp-vectorize"],
+              "potential_softmax.hip": ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang",
+                                        "-packed-fp32-ops"],
               "nuts.hip": ["-ffp-contract=off"],
               "potential_small.hip": ["-ffp-contract=off"],
               "potential_program.hip": ["-ffp-contract=off"],

@@ -9,8 +9,8 @@ differentiates it with JAX.  Here the trace records each site's distribution, pa
 observed data; a matcher per supported structure checks the priors' constants and the
 likelihood's expression and returns the bound fused potential, with the model's own site
 names.  Supported structures: the reference's examples on the hot path (covtype logistic
-regression, eight schools, funnel and its LocScaleReparam(0) form, stochastic volatility,
-the BNN) and the test targets (diagonal normal, multivariate normal).  For anything else
+regression and its multi-class form, softmax regression; eight schools, funnel and its
+LocScaleReparam(0) form, stochastic volatility, the BNN) and the test targets (diagonal normal, multivariate normal).  For anything else
 potential_from_model raises NotImplementedError naming the traced sites; NUTS / HMC then hand
 the model to the program compiler (numpyro_amd/program.py compile_model), which lowers the
 traced log-joint to a straight-line program of primitive operations evaluated, with its
@@ -159,6 +159,28 @@ def _match_logistic(trace):
     return _renamed(P.LogisticRegression(lg.args[0], o.obs), {"coefs": lat[0].name})
 
 
+def _match_softmax(trace):
+    """coefs ~ Normal(0, 1) [D, K], obs ~ Categorical(logits=X @ coefs), integer labels in [0, K)."""
+    lat, obs = _split(trace)
+    if len(lat) != 1 or len(obs) != 1 or not _std_normal(lat[0]) or len(lat[0].shape) != 2:
+        return None
+    o = obs[0]
+    if not _is(o.fn, dist.CategoricalLogits):
+        return None
+    lg = _base(o.fn).logits
+    if not (isinstance(lg, Sym) and lg.op == "matmul" and _const(lg.args[0]) and _latent(lg.args[1], lat[0].name)):
+        return None
+    X, y = lg.args[0], _host(o.obs)
+    D, K = lat[0].shape
+    if tuple(shape_of(X)) != (y.shape[0] if y.ndim == 1 else -1, D) or y.dtype.kind not in "iu":
+        return None
+    if y.size == 0 or y.min() < 0 or y.max() >= K:
+        return None
+    if not (1 <= D <= P.SoftmaxRegression.MAX_FEATURES and 2 <= K <= P.SoftmaxRegression.MAX_CLASSES):
+        return None
+    return _renamed(P.SoftmaxRegression(X, o.obs, K), {"coefs": lat[0].name})
+
+
 def _match_eight_schools(trace):
     """README.md:47-55: mu ~ N(0, 5), tau ~ HalfCauchy(5), theta ~ N(mu, tau) [J], y ~ N(theta, sigma)."""
     lat, obs = _split(trace)
@@ -299,7 +321,7 @@ def _match_normal(trace):
     return None
 
 
-MATCHERS = (_match_logistic, _match_eight_schools, _match_funnel, _match_sv, _match_bnn, _match_normal)
+MATCHERS = (_match_logistic, _match_softmax, _match_eight_schools, _match_funnel, _match_sv, _match_bnn, _match_normal)
 
 
 def potential_from_model(model, args=(), kwargs=None):
@@ -313,7 +335,7 @@ def potential_from_model(model, args=(), kwargs=None):
             return _with_traced_deterministics(pot, trace)
     raise NotImplementedError(
         "no fused kernel for this model structure (sites: " + ", ".join(map(repr, trace.sites.values())) +
-        "); supported: the reference's covtype logistic regression, eight schools, funnel (+ LocScaleReparam), "
+        "); supported: the reference's covtype logistic regression, softmax regression, eight schools, funnel (+ LocScaleReparam), "
         "stochastic volatility and BNN examples, and diagonal / multivariate normal targets")
 
 

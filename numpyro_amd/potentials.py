@@ -233,6 +233,58 @@ class LogisticRegression(Potential):
         return 4.0 * self.N * self.dim * num_chains
 
 
+class SoftmaxRegression(Potential):
+    """Multinomial logistic regression: coefs ~ N(0, 1)^(D x K), obs ~ Categorical(logits=X @ coefs)
+    with integer labels in [0, K) (csrc/potential_softmax.hip)."""
+
+    MAX_FEATURES, MAX_CLASSES = 64, 32
+
+    def __init__(self, data, labels, num_classes):
+        self.X_in, self.y_in = data, labels
+        shape, yshape = tuple(data.shape), tuple(getattr(labels, "shape", None) or np.shape(labels))
+        if len(shape) != 2 or yshape != shape[:1]:
+            raise ValueError(f"softmax regression needs data [N, D] and labels [N] (got {shape}, {yshape})")
+        self.N, self.D, self.K = int(shape[0]), int(shape[1]), int(num_classes)
+        if not 1 <= self.D <= self.MAX_FEATURES:
+            raise ValueError(f"the fused softmax-regression kernel supports 1 to {self.MAX_FEATURES} features "
+                             f"(got {self.D})")
+        if not 2 <= self.K <= self.MAX_CLASSES:
+            raise ValueError(f"the fused softmax-regression kernel supports 2 to {self.MAX_CLASSES} classes "
+                             f"(got {self.K})")
+        self.dim = self.D * self.K
+        self.sites = [("coefs", (self.D, self.K), REAL)]
+        self.packed = None
+
+    slots = 4  # workspaces, as LogisticRegression
+
+    def _bind(self, C, ldc, device):
+        if self.packed is None or self.packed.device != device:
+            X = _dev(self.X_in, device)
+            y = _dev(self.y_in, device, torch.int32)
+            nb = lib().nmx_softmax_packed_bytes(self.N, self.D, self.K)
+            self.packed = torch.empty(nb // 4, dtype=torch.float32, device=device)
+            with torch.cuda.device(device):
+                check(lib().nmx_softmax_pack(ptr(X), ptr(y), self.N, self.D, self.K, ptr(self.packed),
+                                             native.stream_ptr()), "nmx_softmax_pack")
+            del X, y
+        wb = lib().nmx_softmax_workspace_bytes(self.N, self.D, self.K, ldc)  # the slabs' rows are ldc wide
+        self.workspace = torch.empty(wb, dtype=torch.uint8, device=device)
+        self._more_ws = []  # slots 1.. (allocated on first use)
+
+    def evaluate(self, ev, stream, slot=0):
+        ws = self.workspace
+        if slot:
+            while len(self._more_ws) < slot:
+                self._more_ws.append(torch.empty_like(self.workspace))
+            ws = self._more_ws[slot - 1]
+        check(lib().nmx_softmax_pe_grad(ptr(self.packed), self.N, self.D, self.K, ctypes.byref(ev), ptr(ws),
+                                        stream), "nmx_softmax_pe_grad")
+
+    def flops_per_eval(self, num_chains):
+        """Algorithmic FLOPs of one evaluation (two GEMMs): 4 N D K C."""
+        return 4.0 * self.N * self.D * self.K * num_chains
+
+
 class StochasticVolatility(Potential):
     """examples/stochastic_volatility.py:57-65 (sigma ~ Exp(50), s ~ GRW(sigma), nu ~ Exp(0.1),
     r ~ StudentT(nu, 0, exp(s)))."""
@@ -410,6 +462,17 @@ def _fused_model(name):
 logistic_regression = FusedModel(
     "logistic_regression", lambda data, labels, subsample_size=None: LogisticRegression(data, labels),
     "examples/covtype.py:66-71 model(data, labels)")
+
+def _softmax_regression(data, labels, num_classes=None):
+    if num_classes is None:
+        y = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+        num_classes = int(y.max()) + 1
+    return SoftmaxRegression(data, labels, num_classes)
+
+
+softmax_regression = FusedModel(
+    "softmax_regression", _softmax_regression,
+    "coefs ~ Normal(0, 1) [D, K], obs ~ Categorical(logits=X @ coefs): model(data, labels, num_classes=None)")
 
 eight_schools = FusedModel(
     "eight_schools", lambda J, sigma, y=None: EightSchools(J, sigma, y),
