@@ -499,6 +499,33 @@ size_t nmx_softmax_workspace_bytes(int64_t n_rows, int dim, int num_classes, int
 int nmx_softmax_pe_grad(const void* packed, int64_t n_rows, int dim, int num_classes, const nmx_eval_batch* ev,
                         void* workspace, void* stream);
 
+/* The same model after sampling: the pointwise log-likelihood table and posterior predictive
+ * labels for posterior samples W [num_samples][dim][num_classes] (get_samples()["coefs"], row-major),
+ * X [n_rows][dim] and int32 labels that may be any data of that shape, not the training set
+ * (csrc/predictive_softmax.hip: the product transposed, (sample, class) on the M axis and rows on
+ * the N axis, so a sample's classes are registers of one lane and the softmax needs no cross-lane
+ * step; split-bf16 like the potential, so the table agrees with it to float32 accuracy).
+ *   nmx_softmax_loglik   out[s ld + n] = l[n][y_n] - logsumexp_k l[n][k], l = X W_s; NaN where the
+ *                        label is outside [0, num_classes)
+ *   nmx_softmax_predict  out[s ld + n] = a class in [0, num_classes) drawn from softmax(l[n][:]):
+ *                        the first k whose running sum of exp(l_j - max) exceeds u times the whole
+ *                        sum, u = Philox(seed; sample s, site 0, row n) as the other predictive
+ *                        kernels key it, so a draw depends on (seed, sample, row) only
+ * ld >= n_rows is the row stride of `out` in elements (a chunk of samples written into a wider
+ * table); nothing outside out[s][0 .. n_rows), s < num_samples, is written.  X is first split into
+ * bf16 planes in the kernel's fragment order, once per X: nmx_softmax_predictive_pack into a
+ * workspace of nmx_softmax_predictive_workspace_bytes (0 for a shape out of range), which both
+ * kernels then read for any number of launches.  n_rows >= 1, 1 <= dim <= 64,
+ * 2 <= num_classes <= 32, num_samples >= 1, ld >= n_rows and, for draws, n_rows <= 2^24 (the
+ * counter's element field); anything else is NMX_ERR_INVALID with the number named, before any
+ * launch.  A sample's row does not depend on num_samples, its position or ld. */
+size_t nmx_softmax_predictive_workspace_bytes(int64_t n_rows, int dim);
+int nmx_softmax_predictive_pack(const float* X, int64_t n_rows, int dim, void* workspace, void* stream);
+int nmx_softmax_loglik(const void* workspace, const int32_t* y, int64_t n_rows, int dim, int num_classes,
+                       const float* W, int num_samples, float* out, int64_t ld, void* stream);
+int nmx_softmax_predict(const void* workspace, int64_t n_rows, int dim, int num_classes, const float* W,
+                        int num_samples, uint64_t seed, int32_t* out, int64_t ld, void* stream);
+
 /* ---- dense mass matrix (hmc_util.py:1203-1220 dense matvecs, hmc.py:103-108 momentum,
  *      hmc_util.py:612-620 dense Welford finalize) ----
  * With inverse mass M^-1 = T T^T, NUTS with dense mass on z is NUTS with identity mass on

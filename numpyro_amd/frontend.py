@@ -159,26 +159,39 @@ def _match_logistic(trace):
     return _renamed(P.LogisticRegression(lg.args[0], o.obs), {"coefs": lat[0].name})
 
 
-def _match_softmax(trace):
-    """coefs ~ Normal(0, 1) [D, K], obs ~ Categorical(logits=X @ coefs), integer labels in [0, K)."""
-    lat, obs = _split(trace)
-    if len(lat) != 1 or len(obs) != 1 or not _std_normal(lat[0]) or len(lat[0].shape) != 2:
+def softmax_structure(trace):
+    """(coefs site, label site, X) of coefs ~ Normal(0, 1) [D, K], obs ~ Categorical(logits=X @ coefs)
+    with X [N, D] and D, K inside the fused kernels' limits, or None.  The label site may be
+    without data (Predictive draws it): K is the latent's."""
+    sites = list(trace.sites.values())
+    if len(sites) != 2:
         return None
-    o = obs[0]
-    if not _is(o.fn, dist.CategoricalLogits):
+    w, o = sorted(sites, key=lambda s: _is(s.fn, dist.CategoricalLogits))
+    if w.obs is not None or not _std_normal(w) or len(w.shape) != 2 or not _is(o.fn, dist.CategoricalLogits):
         return None
     lg = _base(o.fn).logits
-    if not (isinstance(lg, Sym) and lg.op == "matmul" and _const(lg.args[0]) and _latent(lg.args[1], lat[0].name)):
+    if not (isinstance(lg, Sym) and lg.op == "matmul" and _const(lg.args[0]) and _latent(lg.args[1], w.name)):
         return None
-    X, y = lg.args[0], _host(o.obs)
-    D, K = lat[0].shape
-    if tuple(shape_of(X)) != (y.shape[0] if y.ndim == 1 else -1, D) or y.dtype.kind not in "iu":
-        return None
-    if y.size == 0 or y.min() < 0 or y.max() >= K:
+    X, (D, K) = lg.args[0], w.shape
+    if len(shape_of(X)) != 2 or shape_of(X)[1] != D:
         return None
     if not (1 <= D <= P.SoftmaxRegression.MAX_FEATURES and 2 <= K <= P.SoftmaxRegression.MAX_CLASSES):
         return None
-    return _renamed(P.SoftmaxRegression(X, o.obs, K), {"coefs": lat[0].name})
+    return w, o, X
+
+
+def _match_softmax(trace):
+    """coefs ~ Normal(0, 1) [D, K], obs ~ Categorical(logits=X @ coefs), integer labels in [0, K)."""
+    hit = softmax_structure(trace)
+    if hit is None or hit[1].obs is None:
+        return None
+    w, o, X = hit
+    y, K = _host(o.obs), w.shape[1]
+    if y.ndim != 1 or y.shape[0] != shape_of(X)[0] or y.dtype.kind not in "iu":
+        return None
+    if y.size == 0 or y.min() < 0 or y.max() >= K:
+        return None
+    return _renamed(P.SoftmaxRegression(X, o.obs, K), {"coefs": w.name})
 
 
 def _match_eight_schools(trace):

@@ -12,6 +12,10 @@ Nearly every use reduces that table over the samples (the log pointwise predicti
 examples/baseball.py prints, WAIC): ``pointwise_predictive`` streams the same chunks through the
 pointwise reduce kernels and returns the per-observation lppd and p_waic without holding the
 table.
+
+A model whose trace is the softmax regression of the fused potential (frontend._match_softmax) has a
+rank-2 latent the program compiler refuses: its table comes from the kernel of that structure
+(csrc/predictive_softmax.hip through ``_SoftmaxRun``), with the same chunks, shapes and dictionaries.
 """
 from __future__ import annotations
 
@@ -23,8 +27,10 @@ import torch
 
 from .. import native
 from .. import potentials as P
+from ..frontend import _host, _match_softmax, softmax_structure, trace_model
 from ..native import check, lib, ptr
 from ..pointwise import PointwiseReducer
+from ..softmax_predictive import SoftmaxPredictive
 from .predictive import common_batch_shape
 
 # the tape of one chunk of samples stays under this many bytes
@@ -89,11 +95,62 @@ class _Run:
         return torch.as_tensor(np.asarray(c, np.float32)).to(self.device)
 
 
+class _SoftmaxProgram:
+    """What the three functions read of a program, for the one observed site of a softmax regression."""
+
+    num_ops, constant_outputs = 1, {}
+
+    def __init__(self, site, N):
+        from ..loglik_program import LogLikOutput
+
+        self.num_columns = N
+        self.outputs = [LogLikOutput(site, 0, N, (N,), 0)]
+
+
+class _SoftmaxRun:
+    """The same chunks() / launch() over the fused softmax-regression kernel
+    (csrc/predictive_softmax.hip): X is split once, a chunk of samples is one launch."""
+
+    def __init__(self, W_site, obs_site, X, flat, batch_shape, S, what):
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{what} needs a GPU (the softmax-regression table is a HIP kernel)")
+        self.device = dev = torch.device("cuda", torch.cuda.current_device())
+        self.batch_shape, self.S = batch_shape, S
+        D, self.K = W_site.shape
+        W = flat[W_site.name]
+        if tuple(W.shape[1:]) != (D, self.K):
+            raise ValueError(f"posterior samples of site {W_site.name!r} have shape {tuple(W.shape[1:])} per draw, "
+                             f"the model's site has {(D, self.K)}")
+        self.W = W.to(dev, torch.float32).contiguous()
+        self.kernel = SoftmaxPredictive(X, dev)
+        self.y = torch.as_tensor(np.asarray(_host(obs_site.obs), np.int32)).to(dev)
+        self.prog = _SoftmaxProgram(obs_site.name, self.kernel.N)
+        self.chunk = max(1, min(S, MAX_WORKSPACE_BYTES // (4 * self.kernel.N)))  # the chunk's table under the limit
+
+    chunks = _Run.chunks
+
+    def launch(self, s0, m, out):
+        """Samples [s0, s0 + m) into the rows of ``out`` [>= m, N]."""
+        self.kernel.log_likelihood(self.y, self.W[s0:s0 + m], out)
+
+
+def _run(model, posterior_samples, args, kwargs, batch_ndims, what):
+    """The run of a model's trace: the fused kernel where the trace is the softmax regression that
+    frontend._match_softmax recognises (same structure, limits and labels in range; X and y any data
+    of that shape), the log-likelihood program for every other model."""
+    flat, batch_shape, S = _flatten(model, posterior_samples, batch_ndims, what)
+    trace = trace_model(getattr(model, "_nmx_model", model), args, kwargs, getattr(model, "_nmx_reparam", None))
+    hit = softmax_structure(trace)
+    if hit is None or trace.reparam or hit[0].name not in flat or _match_softmax(trace) is None:
+        return _Run(model, posterior_samples, args, kwargs, batch_ndims, what)
+    return _SoftmaxRun(*hit, flat, batch_shape, S, what)
+
+
 def log_likelihood(model, posterior_samples, *args, parallel=False, batch_ndims=1, **kwargs):
     """numpyro.infer.log_likelihood (numpyro/infer/util.py:1094-1170) for model functions of the
     program compiler's class: {observed site: float32 tensor [*batch_shape, *site_shape]} on the
     current GPU.  ``parallel`` is accepted and ignored (every sample is one wave of one launch)."""
-    run = _Run(model, posterior_samples, args, kwargs, batch_ndims, "log_likelihood")
+    run = _run(model, posterior_samples, args, kwargs, batch_ndims, "log_likelihood")
     prog, S = run.prog, run.S
     out = {}
     if prog.num_ops:
@@ -113,7 +170,7 @@ def pointwise_predictive(model, posterior_samples, *args, batch_ndims=1, **kwarg
     pointwise predictive density logsumexp_s(log p(y_i | theta_s)) - log S and the variance over s
     of log p(y_i | theta_s) (S - 1 in the denominator: NaN for one sample), reduced on the device
     chunk by chunk without holding the [S, N] table."""
-    run = _Run(model, posterior_samples, args, kwargs, batch_ndims, "pointwise_predictive")
+    run = _run(model, posterior_samples, args, kwargs, batch_ndims, "pointwise_predictive")
     prog, S = run.prog, run.S
     out = {}
     if prog.num_ops:
@@ -141,7 +198,7 @@ def loo(model, posterior_samples, *args, batch_ndims=1, reff=1.0, **kwargs):
     at once, so the [S, N] table is held on the device, with the kernel's copy of it."""
     from .. import psis
 
-    run = _Run(model, posterior_samples, args, kwargs, batch_ndims, "loo")
+    run = _run(model, posterior_samples, args, kwargs, batch_ndims, "loo")
     prog, S = run.prog, run.S
     tail = psis.tail_length(S, reff)
     psis.check_sizes(S, tail)

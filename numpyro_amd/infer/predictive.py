@@ -14,7 +14,8 @@ with ``obs=`` does under the reference's Predictive.  Deterministic sites (the m
 ``numpyro.deterministic`` and reparameterised sites such as the non-centred funnel's ``x``,
 reparam.py:140-142) are returned by default, as the reference's ``_predictive`` does
 (util.py:870-877), computed from the posterior samples.  Models: covtype logistic regression
-(``obs``), eight schools (``obs``), BNN (``Y``), stochastic volatility (``r``: its returns are
+(``obs``), softmax regression (``obs``: class labels, csrc/predictive_softmax.hip; also for a model
+function of that structure, which the program path would refuse for its rank-2 latent), eight schools (``obs``), BNN (``Y``), stochastic volatility (``r``: its returns are
 both the observation and the series length, examples/stochastic_volatility.py:57-65, so -- as in
 the reference -- the observed data come back), funnel and its LocScaleReparam form (no observed
 site: deterministic ``x`` and any ``return_sites``, as examples/funnel.py:84-87 uses it).  Out of
@@ -72,6 +73,16 @@ def _predict_logreg(samples, seed, device, data, labels=None, subsample_size=Non
     return {"obs": out}
 
 
+def _predict_softmax(samples, seed, device, data, labels=None, num_classes=None, latent="coefs", site="obs"):
+    """Labels of obs ~ Categorical(logits = X @ coefs) (csrc/predictive_softmax.hip); the number of
+    classes is the samples' last dimension."""
+    from ..softmax_predictive import SoftmaxPredictive
+
+    if labels is not None:
+        return {site: _observed(labels, samples[latent].shape[0], device, torch.int32)}
+    return {site: SoftmaxPredictive(data, device).draw(samples[latent], seed)}
+
+
 def _predict_eight_schools(samples, seed, device, J, sigma, y=None):
     theta = samples["theta"].reshape(-1, J).to(device, torch.float32).contiguous()
     if y is not None:
@@ -112,6 +123,7 @@ def _predict_none(samples, seed, device, *args, **kwargs):
 # FusedModel -> (observed sites, sampler(samples, seed, device, *args, **kwargs))
 _PREDICTORS = {
     "logistic_regression": (("obs",), _predict_logreg),
+    "softmax_regression": (("obs",), _predict_softmax),
     "eight_schools": (("obs",), _predict_eight_schools),
     "bnn": (("Y",), _predict_bnn),
     "stochastic_volatility": (("r",), _predict_sv),
@@ -122,6 +134,8 @@ _PREDICTORS = {
 
 # models whose Predictive draws nothing on the device (no free observed site)
 _HOST_ONLY = {"stochastic_volatility", "funnel", "funnel_reparam"}
+# models without a deterministic site whose potential cannot be built without the observed data
+_NO_DETERMINISTIC = {"softmax_regression"}
 
 
 def common_batch_shape(shapes):
@@ -200,9 +214,11 @@ class Predictive:
         draws = sampler(flat, key_to_seed(rng_key), device, *args, **kwargs)
         # deterministic sites from the (constrained) latent values: recomputed from the samples
         # (exclude_deterministic=True, the default) or taken as given
-        pot = self.model.potential(*args, **kwargs)
-        latent = {n: flat[n] for n, _, _ in pot.sites if n in flat}
-        dets = pot.deterministic(latent) if len(latent) == len(pot.sites) else {}
+        dets = {}
+        if self.model.__name__ not in _NO_DETERMINISTIC:
+            pot = self.model.potential(*args, **kwargs)
+            latent = {n: flat[n] for n, _, _ in pot.sites if n in flat}
+            dets = pot.deterministic(latent) if len(latent) == len(pot.sites) else {}
         if not self.exclude_deterministic:
             dets.update({k: v for k, v in flat.items() if k in dets})
         if self.return_sites is None:
@@ -230,6 +246,10 @@ class Predictive:
 
         nb, S = self.batch_ndims, self.num_samples
         flat = {k: torch.as_tensor(v).reshape(S, *v.shape[nb:]) for k, v in self.posterior_samples.items()}
+        fused = self._softmax_draws(flat, rng_key, args, kwargs)
+        if fused is not None:
+            return {n: v.reshape(*self._batch_shape, *v.shape[1:]) for n, v in fused.items()
+                    if self.return_sites is None or n in self.return_sites}
         prog = compile_predictive(self.model, args, kwargs, given=flat)
         device = prog.sample_device(flat, "Predictive")  # the CPU where nothing is drawn: observed data / given sites
         given = {name: flat[name].to(device, torch.float32) for name, _, _, _ in prog.inputs}
@@ -250,6 +270,26 @@ class Predictive:
             v = draws[n] if n in draws else dets[n] if n in dets else flat[n].to(device) if n in flat else None
             if v is not None:
                 out[n] = v.reshape(*self._batch_shape, *v.shape[1:])
+        return out
+
+    def _softmax_draws(self, flat, rng_key, args, kwargs):
+        """{label site: [S, N], and the given latent under return_sites} where the model's trace is the
+        softmax regression of the fused kernels (frontend.softmax_structure; the label site with or
+        without data) and its latent is among the samples; None for any other model."""
+        from ..frontend import softmax_structure, trace_model
+
+        model = self.model
+        trace = trace_model(getattr(model, "_nmx_model", model), args, kwargs, getattr(model, "_nmx_reparam", None))
+        hit = softmax_structure(trace)
+        if hit is None or trace.reparam or trace.deterministics or hit[0].name not in flat:
+            return None
+        w, o, X = hit
+        if not torch.cuda.is_available():
+            raise RuntimeError("Predictive needs a GPU (the samplers are HIP kernels)")
+        device = torch.device("cuda", torch.cuda.current_device())
+        out = _predict_softmax(flat, key_to_seed(rng_key), device, X, o.obs, latent=w.name, site=o.name)
+        if self.return_sites is not None:
+            out[w.name] = flat[w.name].to(device)
         return out
 
     def _run_program(self, prog, given, seed, device):

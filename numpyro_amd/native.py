@@ -243,6 +243,10 @@ SIGNATURES: dict[str, tuple] = {
     "nmx_softmax_pack": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp]),
     "nmx_softmax_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
     "nmx_softmax_pe_grad": (c_int, [c_vp, c_i64, c_int, c_int, _evp, c_vp, c_vp]),
+    "nmx_softmax_predictive_workspace_bytes": (c_size, [c_i64, c_int]),
+    "nmx_softmax_predictive_pack": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp]),
+    "nmx_softmax_loglik": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_vp, c_i64, c_vp]),
+    "nmx_softmax_predict": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_int, c_u64, c_vp, c_i64, c_vp]),
     "nmx_dense_padded_dim": (c_int, [c_int]),
     "nmx_gemm_chains": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
     "nmx_gemm_chains_workspace_bytes": (c_size, [c_int, c_int]),
