@@ -475,6 +475,24 @@ int nmx_logreg_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_ev
  * do not depend on how many chains or GPUs share the work). */
 int nmx_logreg_num_splits(int64_t n_rows);
 
+/* The same model for 65 <= dim <= 1024 (csrc/potential_logreg_wide.hip): a workgroup's waves are
+ * a grid of chain tiles x feature slices, chosen from dim alone, so a wave holds only its slice's
+ * coefficient fragments and gradient accumulators; the slices' partial logits meet in LDS and are
+ * added in slice order.  Same arithmetic (split-bf16 MFMA, f32-accurate), same argument shapes and
+ * the same determinism as the calls above: the number of row splits depends on n_rows and dim
+ * only, and a chain's results are bitwise independent of the chains sharing the launch.  n_rows
+ * >= 1 and 65 <= dim <= 1024; anything else is NMX_ERR_INVALID with the number named, before any
+ * launch, and 0 from the size functions.  The packed image is this kernel's own (X^T y as float64,
+ * then per 32-row tile the slices' fragment-order pieces and the labels).  The workspace holds
+ * slabs of ldc columns: nmx_logreg_wide_workspace_bytes sizes it for ldc = num_chains rounded up
+ * to 64, so a caller whose arena is wider passes its ldc there. */
+size_t nmx_logreg_wide_packed_bytes(int64_t n_rows, int dim);
+int nmx_logreg_wide_pack(const float* X, const float* y, int64_t n_rows, int dim, void* packed,
+                         void* stream);
+size_t nmx_logreg_wide_workspace_bytes(int64_t n_rows, int dim, int num_chains);
+int nmx_logreg_wide_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch* ev,
+                            void* workspace, void* stream);
+
 /* Softmax (multinomial logistic) regression: coefs ~ N(0,1)^(D x K),
  * obs ~ Categorical(logits = X @ coefs), coordinate of coefs[d][k] = d K + k (ravel order):
  *   U(W)  = sum_n [logsumexp_k l_nk - l_{n, y_n}] + sum_dk [W_dk^2 / 2 + log(2 pi) / 2],  l = X W
@@ -624,7 +642,7 @@ int nmx_pe_mvn(const float* prec_t, int lda, const float* mu, const float* neg_p
  *      sample, observed sites sampled).  Samples are constrained values, [num_samples][...]
  *      row-major; draws are Philox-keyed by (seed, sample, element). ---- */
 /* examples/covtype.py:66-71: obs ~ Bernoulli(logits = X @ coefs); X [n_rows][dim] f32,
- * coefs [num_samples][dim], out [num_samples][n_rows] int32 0/1. */
+ * coefs [num_samples][dim], out [num_samples][n_rows] int32 0/1; dim <= 1024. */
 int nmx_predict_logreg(const float* X, int64_t n_rows, int dim, const float* coefs, int num_samples,
                        uint64_t seed, int32_t* out, void* stream);
 /* README.md:47-55 eight schools: obs ~ Normal(loc, scale); loc [num_samples][n] (theta),

@@ -57,6 +57,8 @@ COMMON_FLAGS = [
 FILE_FLAGS = {"potential_logreg.hip": ["-fno-slp-vectorize"],
               "potential_softmax.hip": ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang",
                                         "-packed-fp32-ops"],
+              "potential_logreg_wide.hip": ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang",
+                                            "-packed-fp32-ops"],
               "nuts.hip": ["-ffp-contract=off"],
               "potential_small.hip": ["-ffp-contract=off"],
               "potential_program.hip": ["-ffp-contract=off"],

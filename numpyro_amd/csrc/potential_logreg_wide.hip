@@ -1,0 +1,636 @@
+// Logistic-regression potential + gradient for 65 <= D <= 1024 features:
+// coefs ~ N(0, 1)^D, obs ~ Bernoulli(logits = X @ coefs).
+//
+//   U(b)  = sum_n [max(l_n, 0) + log1p(exp(-|l_n|)) - y_n l_n] + sum_d [b_d^2 / 2 + log(2 pi) / 2]
+//   dU/db = X^T (sigmoid(l) - y) + b,      l = X b
+//
+// k_logreg_wide: the D-blocked sibling of k_logreg_x3 (potential_logreg.hip).  That kernel keeps a
+// wave's whole coefficient tile (0.75 D VGPRs), all its gradient accumulators (D / 2 VGPRs) and the
+// whole 32-row X tile (384 D bytes of LDS) resident, which ends at D = 64.  Here a workgroup's waves
+// are a grid of CT chain tiles x DS feature slices, both functions of D alone (lw_class):
+//
+//   wave (j, i) owns chain tile j (32 chains) and the features [i DW, (i + 1) DW), DW = 32 DTS,
+//   DTS = 3 or 4; it holds only its slice's coefficient fragments (0.75 DW VGPRs) and its slice's
+//   gradient accumulators (DW / 2 VGPRs).
+//
+// Per 32-row tile
+//   1. GEMM1, sliced: wave (j, i) computes the partial logits of its slice, L_i = X[:, slice i] .
+//      Z[slice i, tile j] (split-bf16, six products per 16-deep k-block, nmx_split_bf16.h), and
+//      writes its 16 accumulator registers to its 4 KiB exchange slot in LDS;
+//   2. after the workgroup barrier every wave of chain tile j adds the DS partials IN SLICE ORDER,
+//      ((L_0 + L_1) + L_2) + ...: all waves of the chain tile hold the same bits, whatever the timing;
+//   3. every wave runs the Bernoulli epilogue itself (redundant VALU work, but no second exchange and
+//      no second barrier); only slice 0 accumulates U (float64 per lane);
+//   4. GEMM2, sliced: G[slice i] += X[:, slice i]^T . R with the residual registers as the B operand
+//      (the accumulator holds the chain on the lane and 16 rows in the registers: the B layout of the
+//      32x32x16 form with the k order permuted, which the packed X^T pieces follow).
+// The N x C logit matrix never exists in memory.
+//
+// X stream.  A wave needs only its slice's pieces, so X never sits in LDS as a whole tile.  The pack
+// orders a tile as DS slices x 2 DTS chunks of six 1 KiB fragment-order pieces (6 KiB: the three
+// planes of 32 features, for GEMM1 as two k-blocks, for GEMM2 as one d-tile x two k-steps), then
+// 256 bytes of labels.  Each slice has a ring of R chunk slots shared by the CT waves of the slice
+// and filled by buffer LDS-DMA (wave (j, i) copies the pieces j, j + CT, ... of its slice's chunk);
+// one workgroup barrier per chunk says "chunk q has landed in every slice, and chunk q - 1's slot is
+// free", after which chunk q + R - 1 is issued into that slot.  The exchange of step 2 rides on the
+// barrier of the first GEMM2 chunk.  LDS = DS R 6 KiB of rings + 4 KiB per wave of exchange + labels.
+//
+// Rows >= n_rows are MASKED: the pack gives them zero X and the label -1, so their residual meets
+// zero X^T columns and their U term is dropped by the label's sign.  Features >= D are zero in the
+// pack and in the coefficient fragments.
+//
+// The linear part of U, sum_n y_n l_n = <X^T y, b>, is a float64 table of the pack
+// (k_logreg_wide_colsums) added once per chain in the finalize.  The gradient is the in-register
+// residual.
+//
+// Work split: grid = chain-tile groups x S row splits, S a function of n_rows and D only
+// (lw_num_splits); split s owns the tiles [s T / S, (s + 1) T / S), each summed in tile order, and
+// the per-split slabs are added in a fixed order by k_logreg_wide_finalize.  Workgroups of one split
+// sit on one XCD (blockIdx % 8).  No float atomics, no order that depends on arrival: a chain's U
+// and dU are bitwise independent of how many chains share the launch, of its position, of a phase
+// mask and of the order of an active list.
+#include <math.h>
+#include <stdlib.h>
+
+#include <algorithm>
+
+#include "nmx_api_internal.h"
+#include "nmx_common.h"
+#include "nmx_split_bf16.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr float LOG2E = 1.4426950408889634f;
+constexpr float LN2 = 0.6931471805599453f;
+constexpr int LW_ROWS = 32;
+constexpr int LW_MIN_D = 65, LW_MAX_D = 1024;
+constexpr int LW_CHUNK = 6 * 1024;  // six pieces
+constexpr int LW_LABEL_BYTES = 256;
+
+// packed buffer: X^T y as float64[1024] | the tiles
+constexpr size_t LW_TILE_OFFSET = (size_t)LW_MAX_D * sizeof(double);
+
+// Shape class of D: CT chain tiles x DS feature slices of DTS d-tiles (32 features) each, and the
+// ring depth R.  D <= 128 runs 4 x 1 (no exchange: the slice is the whole row), not 4 x 2 with
+// half-empty slices: the same MFMAs per wave, four waves fewer per workgroup and no LDS round trip.
+struct lw_shape {
+  int CT, DS, DTS;
+};
+inline lw_shape lw_class(int D) {
+  const int DS = D <= 128 ? 1 : D <= 256 ? 2 : D <= 512 ? 4 : 8;
+  const int CT = D <= 256 ? 4 : D <= 512 ? 2 : 1;
+  const int DTS = (D + 32 * DS - 1) / (32 * DS);  // 3 or 4 for 65 <= D <= 1024
+  return {CT, DS, DTS};
+}
+inline size_t lw_tile_bytes(int D) {
+  const lw_shape c = lw_class(D);
+  return (size_t)c.DS * 12 * c.DTS * 1024 + LW_LABEL_BYTES;
+}
+inline int64_t lw_ntiles(int64_t n) { return (n + LW_ROWS - 1) / LW_ROWS; }
+
+// Row splits: one per 16 tiles, a multiple of 8 for the XCD placement, capped so that the slabs
+// (S D ldc floats) stay at 256 MiB for ldc = 4096 at the widest D of each class.
+int lw_num_splits(int64_t n_rows, int D) {
+  int64_t s = lw_ntiles(n_rows) / 16;
+  s = s / 8 * 8;
+  const int cap = D <= 256 ? 64 : D <= 512 ? 32 : 16;
+  if (s < 8) s = 8;
+  if (s > cap) s = cap;
+  return (int)s;
+}
+
+// xty[d] = sum_n y_n X[n][d] in float64, one workgroup per column, fixed thread count and a
+// fixed-order tree: the value depends on the data only
+constexpr int CS_THREADS = 256;
+__global__ __launch_bounds__(CS_THREADS) void k_logreg_wide_colsums(const float* __restrict__ X,
+                                                                    const float* __restrict__ y, int64_t n, int D,
+                                                                    double* __restrict__ xty) {
+  __shared__ double red[CS_THREADS];
+  const int d = blockIdx.x;
+  double acc = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += CS_THREADS) acc += (double)y[i] * (double)X[i * D + d];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int k = CS_THREADS / 2; k > 0; k >>= 1) {
+    if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    NMX_DCHECK(d < LW_MAX_D);
+    xty[d] = red[0];
+  }
+}
+
+// Packed tile = DS slices x 2 DTS chunks x 6 pieces of 1 KiB, each piece a 64-lane x 16-byte
+// operand fragment in lane order (lane (r, h), elements j = 0..7), then the labels.  Slice i covers
+// the features d0 = 32 DTS i ..:
+//   chunk c < DTS, piece 3 kk + p     GEMM1 A = X[32 rows][16 cols], plane p, k-block 2 c + kk:
+//                                     X[r][d0 + 16 (2 c + kk) + 8 h + j]
+//   chunk DTS + dt, piece 2 p + s     GEMM2 A = X^T[32 cols][16 rows], plane p, d-tile dt, k-step s:
+//                                     X[16 s + 8 (j >> 2) + 4 h + (j & 3)][d0 + 32 dt + r] -- the k
+//                                     order of the GEMM1 accumulator used as the B operand
+//   labels: float[64], entry 16 h + i = y of row (i & 3) + 8 (i >> 2) + 4 h, -1 for rows >= n
+//           (entries 32.. are zero)
+// Rows >= n_rows and features >= D are zero.  One thread per 16 bytes.
+__global__ void k_logreg_wide_pack(const float* __restrict__ X, const float* __restrict__ y, int64_t n, int D, int DS,
+                                   int DTS, int64_t ntiles, char* __restrict__ out) {
+  const int NP = DS * 12 * DTS;                    // pieces of a tile
+  const int64_t per = (int64_t)NP * 64 + LW_LABEL_BYTES / 16;  // 16-byte items of a tile
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ntiles * per) return;
+  const int64_t t = i / per;
+  const int item = (int)(i % per);
+  const int64_t r0 = t * LW_ROWS;
+  char* dst = out + (size_t)t * ((size_t)NP * 1024 + LW_LABEL_BYTES) + (size_t)item * 16;
+  if (item >= NP * 64) {
+    const int q = item - NP * 64;  // labels 4 q .. 4 q + 3
+    f32x4 f = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (q < 8) {
+      const int hh = q >> 2;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int ii = 4 * (q & 3) + k;
+        const int64_t row = r0 + (ii & 3) + 8 * (ii >> 2) + 4 * hh;
+        f[k] = row < n ? y[row] : -1.0f;
+      }
+    }
+    *reinterpret_cast<f32x4*>(dst) = f;
+    return;
+  }
+  const int lane = item & 63, piece = item >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  const int sl = piece / (12 * DTS), rem = piece % (12 * DTS);
+  const int c = rem / 6, e = rem % 6;
+  const int d0 = 32 * DTS * sl;
+  float v[8];
+  int plane;
+  if (c < DTS) {
+    plane = e % 3;
+    const int kb = 2 * c + e / 3;
+    const int64_t row = r0 + r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int d = d0 + 16 * kb + 8 * h + j;
+      v[j] = (row < n && d < D) ? X[row * D + d] : 0.0f;
+    }
+  } else {
+    plane = e >> 1;
+    const int s = e & 1;
+    const int d = d0 + 32 * (c - DTS) + r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int64_t row = r0 + 16 * s + 8 * (j >> 2) + 4 * h + (j & 3);
+      v[j] = (row < n && d < D) ? X[row * D + d] : 0.0f;
+    }
+  }
+  nmx_bf16x8 b1, b2, b3;
+  nmx_split3(v, b1, b2, b3);
+  *reinterpret_cast<nmx_bf16x8*>(dst) = plane == 0 ? b1 : (plane == 1 ? b2 : b3);
+}
+
+// The counted waits of the ring (k_logreg_wide step) assume that the DMA copies are the loop's only
+// vector-memory operations: true of the release build (no scratch; the resource report says so), not
+// of the debug build, whose checks spill -- that build waits for everything.
+#ifdef NMX_DEBUG
+constexpr bool LW_COUNTED_WAITS = false;
+#else
+constexpr bool LW_COUNTED_WAITS = true;
+#endif
+
+template <int N>
+__device__ __forceinline__ void lw_wait_vm() {
+  // s_waitcnt vmcnt(N), other counters untouched (gfx9 encoding)
+  static_assert(N >= 0 && N < 64, "vmcnt range");
+  __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
+}
+
+// LDS accesses by inline asm: a compiler-visible LDS access after the rings' DMA issue gets an
+// s_waitcnt vmcnt(0), which would drain the prefetch.  lw_lds_wait (all reads and writes done), then
+// lw_pin on each value read before its use.
+__device__ __forceinline__ unsigned lw_lds_addr(const char* p) {
+  return (unsigned)(size_t)((__attribute__((address_space(3))) const char*)p);
+}
+template <class T>
+__device__ __forceinline__ void lw_lds_read(T& v, unsigned addr) {
+  static_assert(sizeof(T) == 16, "one ds_read_b128");
+  asm volatile("ds_read_b128 %0, %1" : "=&v"(v) : "v"(addr));
+}
+__device__ __forceinline__ void lw_lds_write(unsigned addr, const f32x4& v) {
+  asm volatile("ds_write_b128 %0, %1" : : "v"(addr), "v"(v) : "memory");
+}
+__device__ __forceinline__ void lw_lds_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+template <class T>
+__device__ __forceinline__ void lw_pin(T& v) {
+  asm volatile("" : "+v"(v));
+}
+
+// Bernoulli-logits epilogue on the summed GEMM1 accumulator (register r = row (r & 3) + 8 (r >> 2)
+// + 4 h of the tile, y4 its labels, -1 on a masked row):
+//   e = exp(-|l|),  u = 1 + e
+//   sigmoid(l) = 1 / u for l >= 0, e / u for l < 0 (full relative precision on both sides)
+//   log1p(e) = log(u) e / (u - 1): the quotient repairs the rounding of u (e itself where u == 1)
+//   res = sigmoid(l) - y;   U term max(l, 0) + log1p(e), added to `pe` when ACC (slice 0)
+template <bool ACC>
+__device__ __forceinline__ void lw_epilogue(const nmx_f32x16& acc, const f32x4 (&y4)[4], float (&res)[16], double& pe) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float l = acc[r], yv = y4[r >> 2][r & 3];
+    const float e = __builtin_amdgcn_exp2f(-fabsf(l) * LOG2E);
+    const float u = 1.0f + e;
+    const float s = __builtin_amdgcn_rcpf(u);
+    res[r] = (l >= 0.0f ? s : e * s) - yv;
+    if constexpr (ACC) {
+      const float dm = u - 1.0f;
+      const float lg = __builtin_amdgcn_logf(u) * LN2;
+      const float l1p = dm == 0.0f ? e : lg * (e * __builtin_amdgcn_rcpf(dm));
+      pe += yv >= 0.0f ? (double)(fmaxf(l, 0.0f) + l1p) : 0.0;
+    }
+  }
+}
+
+template <int CT, int DS, int DTS, int R>
+struct lw_cfg {
+  static constexpr int WAVES = CT * DS, NCH = 2 * DTS, KBS = 2 * DTS, DW = 32 * DTS;
+  static constexpr int SLICE_BYTES = 12 * DTS * 1024;
+  static constexpr int TILE_BYTES = DS * SLICE_BYTES + LW_LABEL_BYTES;
+  // LDS: the waves' label slots | the slices' rings | the waves' exchange slots
+  static constexpr int LAB_OFF = 0;
+  static constexpr int RING_OFF = WAVES * 2 * LW_LABEL_BYTES;
+  static constexpr int EXCH_OFF = RING_OFF + DS * R * LW_CHUNK;
+  static constexpr int LDS_BYTES = EXCH_OFF + (DS > 1 ? WAVES * 4096 : 0);
+  // pieces of a chunk that wave (j, .) copies: j, j + CT, ... < 6
+  static constexpr int MAX_COPIES = (6 + CT - 1) / CT;
+  static_assert(R == 2 || R == 3, "ring depth");
+  static_assert(LDS_BYTES <= 160 * 1024, "the CU's LDS");
+};
+
+template <int CT, int DS, int DTS, int R>
+__global__ __launch_bounds__(64 * CT * DS) void k_logreg_wide(const char* __restrict__ Xq, int64_t ntiles, int D,
+                                                              int S, int Gt, nmx_eval_batch ev,
+                                                              float* __restrict__ gpart,
+                                                              double* __restrict__ pepart) {
+  using C = lw_cfg<CT, DS, DTS, R>;
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  // splits sp = x (mod 8) run on XCD x (workgroup b = x mod 8), the chain-tile groups of a split on
+  // consecutive workgroups of that XCD, so they share X tiles in its L2
+  const int b = blockIdx.x, qb = b >> 3;
+  const int ct = qb % Gt, split = (qb / Gt) * 8 + (b & 7);
+  const int npos = ev.active_idx ? *ev.active_count : ev.ldc;
+  if (ct * CT * 32 >= npos) return;  // past the compacted list: workgroup-uniform
+
+  const int lane = threadIdx.x & 63;
+  const int wu = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int sl = wu % DS, jt = wu / DS;  // feature slice, chain tile
+  const int h = lane >> 5, col = lane & 31;
+  const int ldc = ev.ldc;
+  const int pos = (ct * CT + jt) * 32 + col;
+  const int c = pos < ldc ? nmx_eval_chain(ev, pos) : -1;
+  const bool active = __any(c >= 0);      // wave-uniform, and the same in every slice of a chain tile
+  if (!__syncthreads_or(active)) return;  // workgroup-uniform
+
+  const int64_t t0 = (int64_t)split * ntiles / S, t1 = (int64_t)(split + 1) * ntiles / S;
+  const int nt = (int)(t1 - t0);
+  const int nq = nt * C::NCH;  // chunks of this split, per slice
+  NMX_DCHECK(split < S && t0 >= 0 && t1 <= ntiles && nt >= 0);
+  const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(Xq + (size_t)t0 * C::TILE_BYTES), 0, (int)((size_t)nt * C::TILE_BYTES), 0x00020000);
+
+  // coefficient fragments of the slice (B operand: lane (col, h) holds Z[d0 + 16 kb + 8 h + j] of
+  // its chain), gathered from the arena once and split; features >= D and lanes without a chain
+  // hold zero
+  // (clamped loads, masked after: a load under `ok` compiles to a branch and a wait per element)
+  const int d0 = sl * C::DW;
+  const int cz = c >= 0 ? c : 0;
+  nmx_bf16x8 z1[C::KBS], z2[C::KBS], z3[C::KBS];
+#pragma unroll
+  for (int kb = 0; kb < C::KBS; ++kb) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int d = d0 + 16 * kb + 8 * h + j;
+      NMX_DCHECK(d >= 0 && cz < ldc);
+      v[j] = ev.z[(size_t)(d < D ? d : D - 1) * ldc + cz];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = (c >= 0 && d0 + 16 * kb + 8 * h + j < D) ? v[j] : 0.0f;
+    nmx_split3(v, z1[kb], z2[kb], z3[kb]);
+  }
+  nmx_f32x16 g[DTS];
+#pragma unroll
+  for (int dt = 0; dt < DTS; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) g[dt][r] = 0.0f;
+  double pe = 0.0;
+
+  char* const ring = lds + C::RING_OFF + sl * R * LW_CHUNK;      // the slice's R chunk slots
+  char* const lab = lds + C::LAB_OFF + wu * 2 * LW_LABEL_BYTES;  // the wave's two label slots
+  // chunk cc of tile kt (q = kt NCH + cc) into slot q % R; with a tile's first chunk every wave
+  // also fetches the tile's labels into its own slot kt & 1
+  auto issue = [&](int kt, int cc) {
+    const int q = kt * C::NCH + cc;
+    NMX_DCHECK(kt >= 0 && kt < nt && cc >= 0 && cc < C::NCH);
+    const unsigned tile = (unsigned)kt * (unsigned)C::TILE_BYTES;
+    if (cc == 0)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)(lab + (kt & 1) * LW_LABEL_BYTES),
+                                               4, lane * 4, tile + (unsigned)(DS * C::SLICE_BYTES), 0, 0);
+    char* dst = ring + (q % R) * LW_CHUNK;
+    const unsigned src = tile + (unsigned)(sl * C::SLICE_BYTES + cc * LW_CHUNK);
+#pragma unroll
+    for (int k = 0; k < C::MAX_COPIES; ++k) {
+      const int e = jt + CT * k;
+      NMX_DCHECK(e >= 6 || (dst + e * 1024 + 1024 <= lds + C::EXCH_OFF && src + e * 1024 + 1024 <= (unsigned)nt * C::TILE_BYTES));
+      if (e < 6)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)(dst + e * 1024), 16,
+                                                 lane * 16, src + (unsigned)(e * 1024), 0, 0);
+    }
+  };
+  // chunk q has landed in every wave and every wave is done with chunk q - 1's slot; then chunk
+  // q + R - 1 goes into that slot.  The copies return in order: with R = 3 the wave's copies of
+  // chunk q + 1 (as many as its copies of any chunk; a label fetch ahead of them is waited for too)
+  // may stay in flight, with R = 2 or at the stream's end nothing is in flight behind chunk q.
+  auto step = [&](int kt, int cc) {
+    const int q = kt * C::NCH + cc;
+    if (R == 2 || q + 1 >= nq || !LW_COUNTED_WAITS) lw_wait_vm<0>();
+    else if (CT == 4 && jt >= 2) lw_wait_vm<1>();
+    else lw_wait_vm<C::MAX_COPIES>();
+    lw_lds_wait();  // the wave's exchange writes
+    asm volatile("s_barrier" ::: "memory");
+    const int cn = (cc + R - 1) % C::NCH, kn = kt + (cc + R - 1) / C::NCH;
+    if (kn < nt) issue(kn, cn);
+  };
+#pragma unroll
+  for (int q = 0; q < R - 1; ++q)
+    if (q < nq) issue(0, q);  // R - 1 <= NCH: chunks of tile 0
+
+  for (int kt = 0; kt < nt; ++kt) {
+    nmx_f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    // GEMM1: the slice's partial logits, two k-blocks per chunk
+#pragma unroll
+    for (int cc = 0; cc < DTS; ++cc) {
+      step(kt, cc);
+      if (!active) continue;
+      const unsigned slot = lw_lds_addr(ring + ((kt * C::NCH + cc) % R) * LW_CHUNK) + lane * 16;
+      nmx_bf16x8 a[2][3];
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int p = 0; p < 3; ++p) lw_lds_read(a[kk][p], slot + (3 * kk + p) * 1024);
+      lw_lds_wait();
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int p = 0; p < 3; ++p) lw_pin(a[kk][p]);
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const int kb = 2 * cc + kk;
+        acc = nmx_mma_bf16(a[kk][2], z1[kb], acc);
+        acc = nmx_mma_bf16(a[kk][1], z2[kb], acc);
+        acc = nmx_mma_bf16(a[kk][0], z3[kb], acc);
+        acc = nmx_mma_bf16(a[kk][1], z1[kb], acc);
+        acc = nmx_mma_bf16(a[kk][0], z2[kb], acc);
+        acc = nmx_mma_bf16(a[kk][0], z1[kb], acc);
+      }
+    }
+    if constexpr (DS > 1) {
+      // the partial goes to the wave's exchange slot: registers 4 k .. 4 k + 3 at k KiB + 16 lane
+      if (active) {
+        // The stores are inline asm, which the compiler's hazard pass does not look into: the wait
+        // states between the last MFMA's write of `acc` and an LDS instruction reading it (18 for a
+        // 16-pass MFMA) are spent here by hand.  Without them the store sends the accumulator short
+        // of its last products.
+        asm volatile("s_nop 15\n\ts_nop 15" : "+v"(acc));
+        const unsigned ex = lw_lds_addr(lds + C::EXCH_OFF + wu * 4096) + lane * 16;
+        NMX_DCHECK(C::EXCH_OFF + wu * 4096 + 4096 <= C::LDS_BYTES);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const f32x4 v = {acc[4 * k], acc[4 * k + 1], acc[4 * k + 2], acc[4 * k + 3]};
+          lw_lds_write(ex + k * 1024, v);
+        }
+      }
+    }
+    nmx_bf16x8 rs[2][3];
+    // GEMM2: the slice's gradient rows, one d-tile per chunk
+#pragma unroll
+    for (int dt = 0; dt < DTS; ++dt) {
+      step(kt, DTS + dt);
+      if (!active) continue;
+      if (dt == 0) {
+        if constexpr (DS > 1) {
+          // the chain tile's DS partials, added in slice order (the next exchange write is several
+          // barriers away: one slot per wave is enough)
+          const unsigned ex = lw_lds_addr(lds + C::EXCH_OFF + jt * DS * 4096) + lane * 16;
+#pragma unroll
+          for (int i = 0; i < DS; ++i) {
+            f32x4 p[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) lw_lds_read(p[k], ex + i * 4096 + k * 1024);
+            lw_lds_wait();
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              lw_pin(p[k]);
+#pragma unroll
+              for (int m = 0; m < 4; ++m) acc[4 * k + m] = i == 0 ? p[k][m] : acc[4 * k + m] + p[k][m];
+            }
+          }
+        }
+        f32x4 y4[4];
+        const unsigned la = lw_lds_addr(lab + (kt & 1) * LW_LABEL_BYTES) + 64 * h;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) lw_lds_read(y4[k], la + 16 * k);
+        lw_lds_wait();
+#pragma unroll
+        for (int k = 0; k < 4; ++k) lw_pin(y4[k]);
+        float res[16];
+        if (sl == 0) lw_epilogue<true>(acc, y4, res, pe);
+        else lw_epilogue<false>(acc, y4, res, pe);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          float v[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] = res[8 * s + j];
+          nmx_split3(v, rs[s][0], rs[s][1], rs[s][2]);
+        }
+      }
+      const unsigned slot = lw_lds_addr(ring + ((kt * C::NCH + DTS + dt) % R) * LW_CHUNK) + lane * 16;
+      nmx_bf16x8 bt[3][2];
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) lw_lds_read(bt[p][s], slot + (2 * p + s) * 1024);
+      lw_lds_wait();
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) lw_pin(bt[p][s]);
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        g[dt] = nmx_mma_bf16(bt[2][s], rs[s][0], g[dt]);
+        g[dt] = nmx_mma_bf16(bt[1][s], rs[s][1], g[dt]);
+        g[dt] = nmx_mma_bf16(bt[0][s], rs[s][2], g[dt]);
+        g[dt] = nmx_mma_bf16(bt[1][s], rs[s][0], g[dt]);
+        g[dt] = nmx_mma_bf16(bt[0][s], rs[s][1], g[dt]);
+        g[dt] = nmx_mma_bf16(bt[0][s], rs[s][0], g[dt]);
+      }
+    }
+  }
+  // a split without a tile stores its zeros: the finalize adds every slab
+  if (c < 0) return;
+  NMX_DCHECK(pos < ldc);
+#pragma unroll
+  for (int dt = 0; dt < DTS; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int d = d0 + 32 * dt + (r & 3) + 8 * (r >> 2) + 4 * h;
+      if (d < D) gpart[((size_t)split * D + d) * ldc + pos] = g[dt][r];
+    }
+  if (sl == 0) {
+    // the two lane halves hold the rows' two halves; lane + 32 is the same chain
+    const double p = pe + __shfl_xor(pe, 32);
+    if (h == 0) pepart[(size_t)split * ldc + pos] = p;
+  }
+}
+
+// One workgroup per (64 batch positions, coordinate j or the U row j = D).  Wave w sums the slabs
+// [w S / 4, (w + 1) S / 4) in order -- and, on the U row, its quarter of the coordinates'
+// z^2 / 2 - xty z in float64 -- then the four wave sums are added in wave order.
+constexpr int FIN_WAVES = 4;
+__global__ __launch_bounds__(64 * FIN_WAVES) void k_logreg_wide_finalize(const float* __restrict__ gpart,
+                                                                         const double* __restrict__ pepart, int S,
+                                                                         int D, nmx_eval_batch ev,
+                                                                         const double* __restrict__ xty) {
+  __shared__ double part[FIN_WAVES][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int pos = blockIdx.x * 64 + lane;
+  const int j = blockIdx.y;
+  const int ldc = ev.ldc;
+  const int c = pos < ldc ? nmx_eval_chain(ev, pos) : -1;
+  const int sp0 = w * S / FIN_WAVES, sp1 = (w + 1) * S / FIN_WAVES;
+  if (c >= 0) {
+    double s = 0.0;
+    if (j < D) {
+      float f = 0.0f;
+      for (int sp = sp0; sp < sp1; ++sp) f += gpart[((size_t)sp * D + j) * ldc + pos];
+      s = f;
+    } else {
+      for (int sp = sp0; sp < sp1; ++sp) s += pepart[(size_t)sp * ldc + pos];
+      const int j0 = w * D / FIN_WAVES, j1 = (w + 1) * D / FIN_WAVES;
+      double q = 0.0;
+      for (int jj = j0; jj < j1; ++jj) {
+        const double z = ev.z[(size_t)jj * ldc + c];
+        q += 0.5 * z * z - xty[jj] * z;
+      }
+      s += q;
+    }
+    part[w][lane] = s;
+  }
+  __syncthreads();
+  if (w != 0 || c < 0) return;
+  if (j < D) {
+    float s = 0.0f;
+#pragma unroll
+    for (int i = 0; i < FIN_WAVES; ++i) s += (float)part[i][lane];
+    const size_t idx = (size_t)j * ldc + c;
+    ev.grad[idx] = ev.z[idx] + s;
+  } else {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < FIN_WAVES; ++i) s += part[i][lane];
+    ev.pe[c] = (float)(s + 0.9189385332046727 * D);
+  }
+}
+
+bool lw_shape_ok(int64_t n_rows, int dim) { return n_rows > 0 && dim >= LW_MIN_D && dim <= LW_MAX_D; }
+
+int lw_check_shape(const char* what, int64_t n_rows, int dim) {
+  if (n_rows <= 0)
+    return nmx_fail(NMX_ERR_INVALID, "%s: need n_rows >= 1 (got n_rows = %lld)", what, (long long)n_rows);
+  if (dim < LW_MIN_D || dim > LW_MAX_D)
+    return nmx_fail(NMX_ERR_INVALID, "%s: need %d <= dim <= %d (got dim = %d)", what, LW_MIN_D, LW_MAX_D, dim);
+  // a split's tiles are addressed by 32-bit byte offsets
+  const int64_t per = lw_ntiles(n_rows) / lw_num_splits(n_rows, dim) + 1;
+  if (per * (int64_t)lw_tile_bytes(dim) >= (int64_t)1 << 31)
+    return nmx_fail(NMX_ERR_INVALID, "%s: n_rows = %lld is past the kernel's 2 GiB of tiles per row split", what,
+                    (long long)n_rows);
+  return NMX_OK;
+}
+
+template <int CT, int DS, int DTS, int R>
+int lw_launch(dim3 grid, hipStream_t s, const char* Xq, int64_t nt, int D, int S, int Gt, const nmx_eval_batch& ev,
+              float* gpart, double* pepart) {
+  using C = lw_cfg<CT, DS, DTS, R>;
+  if (int st = nmx_lds_limit((const void*)k_logreg_wide<CT, DS, DTS, R>, C::LDS_BYTES, s, "k_logreg_wide")) return st;
+  hipLaunchKernelGGL((k_logreg_wide<CT, DS, DTS, R>), grid, dim3(64 * C::WAVES), C::LDS_BYTES, s, Xq, nt, D, S, Gt, ev,
+                     gpart, pepart);
+  return NMX_OK;
+}
+template <int CT, int DS, int R>
+int lw_launch_dts(int DTS, dim3 grid, hipStream_t s, const char* Xq, int64_t nt, int D, int S, int Gt,
+                  const nmx_eval_batch& ev, float* gpart, double* pepart) {
+  if (DTS == 3) return lw_launch<CT, DS, 3, R>(grid, s, Xq, nt, D, S, Gt, ev, gpart, pepart);
+  return lw_launch<CT, DS, 4, R>(grid, s, Xq, nt, D, S, Gt, ev, gpart, pepart);
+}
+
+}  // namespace
+
+extern "C" size_t nmx_logreg_wide_packed_bytes(int64_t n_rows, int dim) {
+  if (!lw_shape_ok(n_rows, dim)) return 0;
+  return LW_TILE_OFFSET + (size_t)lw_ntiles(n_rows) * lw_tile_bytes(dim);
+}
+
+extern "C" int nmx_logreg_wide_pack(const float* X, const float* y, int64_t n_rows, int dim, void* packed,
+                                    void* stream) {
+  if (int st = lw_check_shape("logreg_wide_pack", n_rows, dim)) return st;
+  if (!X || !y || !packed) return nmx_fail(NMX_ERR_INVALID, "logreg_wide_pack: NULL pointer");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_logreg_wide_colsums, dim3(dim), dim3(CS_THREADS), 0, s, X, y, n_rows, dim, (double*)packed);
+  if (int st = nmx_check_launch("k_logreg_wide_colsums")) return st;
+  const lw_shape c = lw_class(dim);
+  const int64_t nt = lw_ntiles(n_rows);
+  const int64_t nthreads = nt * (int64_t)(lw_tile_bytes(dim) / 16);
+  hipLaunchKernelGGL(k_logreg_wide_pack, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, s, X, y, n_rows, dim,
+                     c.DS, c.DTS, nt, (char*)packed + LW_TILE_OFFSET);
+  return nmx_check_launch("k_logreg_wide_pack");
+}
+
+extern "C" size_t nmx_logreg_wide_workspace_bytes(int64_t n_rows, int dim, int num_chains) {
+  if (!lw_shape_ok(n_rows, dim) || num_chains <= 0) return 0;
+  const size_t ldc = (size_t)(num_chains + 63) / 64 * 64;
+  const size_t S = lw_num_splits(n_rows, dim);
+  const size_t g = S * dim * ldc * sizeof(float);
+  const size_t p = S * ldc * sizeof(double);
+  return (g + 255) / 256 * 256 + p;
+}
+
+extern "C" int nmx_logreg_wide_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch* ev,
+                                       void* workspace, void* stream) {
+  if (int st = lw_check_shape("logreg_wide_pe_grad", n_rows, dim)) return st;
+  if (!ev || !ev->z || !ev->grad || !ev->pe)
+    return nmx_fail(NMX_ERR_INVALID, "logreg_wide_pe_grad: eval batch has NULL pointers");
+  if (ev->num_chains <= 0 || ev->ldc < ev->num_chains || ev->ldc % 64)
+    return nmx_fail(NMX_ERR_INVALID, "logreg_wide_pe_grad: bad num_chains/ldc (%d/%d)", ev->num_chains, ev->ldc);
+  if (!packed || !workspace) return nmx_fail(NMX_ERR_INVALID, "logreg_wide_pe_grad: NULL packed/workspace");
+  hipStream_t s = (hipStream_t)stream;
+  const int S = lw_num_splits(n_rows, dim);
+  float* gpart = (float*)workspace;
+  double* pepart = (double*)((char*)workspace + ((size_t)S * dim * ev->ldc * sizeof(float) + 255) / 256 * 256);
+  const int64_t nt = lw_ntiles(n_rows);
+  const lw_shape c = lw_class(dim);
+  const char* Xq = (const char*)packed + LW_TILE_OFFSET;
+  const int nb = std::min(ev->num_chains, ev->ldc);  // batch positions that can hold a chain
+  const int Gt = (nb + 32 * c.CT - 1) / (32 * c.CT);
+  const dim3 grid((unsigned)Gt * S);
+  int st;
+  if (c.DS == 1) st = lw_launch_dts<4, 1, 3>(c.DTS, grid, s, Xq, nt, dim, S, Gt, *ev, gpart, pepart);
+  else if (c.DS == 2) st = lw_launch_dts<4, 2, 3>(c.DTS, grid, s, Xq, nt, dim, S, Gt, *ev, gpart, pepart);
+  else if (c.DS == 4) st = lw_launch_dts<2, 4, 3>(c.DTS, grid, s, Xq, nt, dim, S, Gt, *ev, gpart, pepart);
+  else st = lw_launch_dts<1, 8, 2>(c.DTS, grid, s, Xq, nt, dim, S, Gt, *ev, gpart, pepart);
+  if (st) return st;
+  if (int e = nmx_check_launch("k_logreg_wide")) return e;
+  hipLaunchKernelGGL(k_logreg_wide_finalize, dim3((nb + 63) / 64, dim + 1), dim3(64 * FIN_WAVES), 0, s, gpart, pepart,
+                     S, dim, *ev, (const double*)packed);
+  return nmx_check_launch("k_logreg_wide_finalize");
+}

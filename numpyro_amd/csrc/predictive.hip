@@ -19,12 +19,13 @@ __device__ __forceinline__ nmx_u4 pred_rng(uint64_t seed, int s, int site, int64
 
 // covtype (examples/covtype.py:66-71): obs ~ Bernoulli(logits = data . coefs).  Block =
 // 256 rows of one sample; the sample's coefficients in LDS.
+constexpr int PRED_LOGREG_MAX_D = 1024;  // the widest fused potential (potential_logreg_wide.hip)
 __global__ __launch_bounds__(256) void k_predict_logreg(const float* __restrict__ X, int64_t N, int D,
                                                         const float* __restrict__ coefs, uint64_t seed,
                                                         int32_t* __restrict__ out) {
-  __shared__ float w[64];
+  __shared__ float w[PRED_LOGREG_MAX_D];
   const int s = blockIdx.y;
-  if (threadIdx.x < D) w[threadIdx.x] = coefs[(size_t)s * D + threadIdx.x];
+  for (int d = threadIdx.x; d < D; d += blockDim.x) w[d] = coefs[(size_t)s * D + d];
   __syncthreads();
   const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
@@ -100,8 +101,9 @@ size_t bnn_lds_bytes(int N, int Dx, int H, int Dy) {
 extern "C" int nmx_predict_logreg(const float* X, int64_t n_rows, int dim, const float* coefs, int num_samples,
                                   uint64_t seed, int32_t* out, void* stream) {
   if (!X || !coefs || !out) return nmx_fail(NMX_ERR_INVALID, "predict_logreg: NULL pointer");
-  if (n_rows <= 0 || dim <= 0 || dim > 64 || num_samples <= 0 || num_samples > 65535)
-    return nmx_fail(NMX_ERR_INVALID, "predict_logreg: need n_rows > 0, 0 < dim <= 64, 0 < samples < 65536");
+  if (n_rows <= 0 || dim <= 0 || dim > PRED_LOGREG_MAX_D || num_samples <= 0 || num_samples > 65535)
+    return nmx_fail(NMX_ERR_INVALID, "predict_logreg: need n_rows > 0, 0 < dim <= %d, 0 < samples < 65536",
+                    PRED_LOGREG_MAX_D);
   if (n_rows > 0x00FFFFFF) return nmx_fail(NMX_ERR_INVALID, "predict_logreg: at most 2^24 rows per call");
   const dim3 grid((unsigned)((n_rows + 255) / 256), num_samples);
   hipLaunchKernelGGL(k_predict_logreg, grid, dim3(256), 0, (hipStream_t)stream, X, n_rows, dim, coefs, seed, out);

@@ -191,16 +191,24 @@ class EightSchools(Potential):
 
 
 class LogisticRegression(Potential):
-    """examples/covtype.py:66-71 (coefs ~ N(0, 1)^D, obs ~ Bernoulli(logits=X @ coefs))."""
+    """examples/covtype.py:66-71 (coefs ~ N(0, 1)^D, obs ~ Bernoulli(logits=X @ coefs)).  Up to 64
+    features run on csrc/potential_logreg.hip, 65 to 1024 on the D-blocked kernel of
+    csrc/potential_logreg_wide.hip (the ``nmx_logreg_wide_*`` entry points, same arguments)."""
+
+    MAX_FEATURES = 1024
 
     def __init__(self, data, labels):
         self.X_in, self.y_in = data, labels
         shape = tuple(data.shape)
         self.N, self.dim = int(shape[0]), int(shape[1])
-        if self.dim > 64:
-            raise ValueError("the fused logistic-regression kernel supports up to 64 features")
+        if self.dim > self.MAX_FEATURES:
+            raise ValueError(f"the fused logistic-regression kernels support up to {self.MAX_FEATURES} features "
+                             f"(got {self.dim})")
         self.sites = [("coefs", (self.dim,), REAL)]
         self.packed = None
+
+    def _entry(self, name):
+        return getattr(lib(), ("nmx_logreg_wide_" if self.dim > 64 else "nmx_logreg_") + name)
 
     # workspaces: one per chain group evaluated concurrently (Engine chain groups, one stream each)
     slots = 4
@@ -209,13 +217,14 @@ class LogisticRegression(Potential):
         if self.packed is None or self.packed.device != device:
             X = _dev(self.X_in, device)
             y = _dev(self.y_in, device)
-            nb = lib().nmx_logreg_packed_bytes(self.N, self.dim)
+            nb = self._entry("packed_bytes")(self.N, self.dim)
             self.packed = torch.empty(nb // 4, dtype=torch.float32, device=device)
             with torch.cuda.device(device):
-                check(lib().nmx_logreg_pack(ptr(X), ptr(y), self.N, self.dim, ptr(self.packed),
-                                            native.stream_ptr()), "nmx_logreg_pack")
+                check(self._entry("pack")(ptr(X), ptr(y), self.N, self.dim, ptr(self.packed),
+                                          native.stream_ptr()), "nmx_logreg_pack")
             del X, y
-        wb = lib().nmx_logreg_workspace_bytes(self.N, self.dim, C)
+        # the wide kernel's slabs have rows of ldc columns
+        wb = self._entry("workspace_bytes")(self.N, self.dim, ldc if self.dim > 64 else C)
         self.workspace = torch.empty(wb, dtype=torch.uint8, device=device)
         self._more_ws = []  # slots 1.. (allocated on first use)
 
@@ -225,8 +234,8 @@ class LogisticRegression(Potential):
             while len(self._more_ws) < slot:
                 self._more_ws.append(torch.empty_like(self.workspace))
             ws = self._more_ws[slot - 1]
-        check(lib().nmx_logreg_pe_grad(ptr(self.packed), self.N, self.dim, ctypes.byref(ev),
-                                       ptr(ws), stream), "nmx_logreg_pe_grad")
+        check(self._entry("pe_grad")(ptr(self.packed), self.N, self.dim, ctypes.byref(ev),
+                                     ptr(ws), stream), "nmx_logreg_pe_grad")
 
     def flops_per_eval(self, num_chains):
         """Algorithmic FLOPs of one evaluation (two GEMMs): 4 N D C."""
