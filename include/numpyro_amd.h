@@ -493,6 +493,27 @@ size_t nmx_logreg_wide_workspace_bytes(int64_t n_rows, int dim, int num_chains);
 int nmx_logreg_wide_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch* ev,
                             void* workspace, void* stream);
 
+/* Poisson (count) regression on the same D-blocked kernel, with the likelihood as a compile-time
+ * policy (csrc/potential_logreg_wide.hip): coefs ~ N(0,1)^D, obs ~ Poisson(exp(X @ coefs + offset)),
+ *   U(b)  = sum_n [mu_n - y_n eta_n + lgamma(y_n + 1)] + sum_d [b_d^2 / 2 + log(2 pi) / 2]
+ *   dU/db = X^T (mu - y) + b,      eta = X b + offset,  mu = exp(eta)
+ * n_rows >= 1 and 1 <= dim <= 1024 (dim <= 64 runs the 4 x 1 class with one or two 32-feature
+ * tiles); anything else is NMX_ERR_INVALID with the number named, before any launch, and 0 from the
+ * size functions.  X [n_rows][dim] float, the counts y [n_rows] as floats and offset [n_rows] float
+ * or NULL (zero) are device pointers.  nmx_poisson_pack synchronises the stream once and fails,
+ * naming the first such row, on a count that is negative, not whole or >= 2^24.  The packed image
+ * holds X^T y and the scalar sum_n lgamma(y_n + 1) - sum_n y_n offset_n as float64 (fixed-order
+ * reductions), then the tiles with y and the offset side by side in the tile's side slot.  A chain
+ * whose eta passes float32's exp range gets U = +inf (never NaN) and may get a non-finite gradient;
+ * no other chain of the launch changes by a bit.  Workspace, eval batch and determinism as
+ * nmx_logreg_wide_*. */
+size_t nmx_poisson_packed_bytes(int64_t n_rows, int dim);
+int nmx_poisson_pack(const float* X, const float* y, const float* offset, int64_t n_rows, int dim, void* packed,
+                     void* stream);
+size_t nmx_poisson_workspace_bytes(int64_t n_rows, int dim, int num_chains);
+int nmx_poisson_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch* ev, void* workspace,
+                        void* stream);
+
 /* Softmax (multinomial logistic) regression: coefs ~ N(0,1)^(D x K),
  * obs ~ Categorical(logits = X @ coefs), coordinate of coefs[d][k] = d K + k (ravel order):
  *   U(W)  = sum_n [logsumexp_k l_nk - l_{n, y_n}] + sum_dk [W_dk^2 / 2 + log(2 pi) / 2],  l = X W

@@ -10,7 +10,7 @@
 // are a grid of CT chain tiles x DS feature slices, both functions of D alone (lw_class):
 //
 //   wave (j, i) owns chain tile j (32 chains) and the features [i DW, (i + 1) DW), DW = 32 DTS,
-//   DTS = 3 or 4; it holds only its slice's coefficient fragments (0.75 DW VGPRs) and its slice's
+//   DTS = 3 or 4 (1 or 2 below 65 features); it holds only its slice's coefficient fragments (0.75 DW VGPRs) and its slice's
 //   gradient accumulators (DW / 2 VGPRs).
 //
 // Per 32-row tile
@@ -49,6 +49,22 @@
 // sit on one XCD (blockIdx % 8).  No float atomics, no order that depends on arrival: a chain's U
 // and dU are bitwise independent of how many chains share the launch, of its position, of a phase
 // mask and of the order of an active list.
+//
+// The likelihood is a compile-time policy LK of the pack, the kernel and the finalize (what the
+// tile's 256-byte side slot holds, the pointwise step between the GEMMs, the constants of U);
+// everything above is shared.  lk_bernoulli is the model above.  lk_poisson is count regression,
+// coefs ~ N(0, 1)^D, obs ~ Poisson(exp(X @ coefs + offset)), 1 <= D <= 1024:
+//
+//   U(b)  = sum_n [mu_n - y_n eta_n + lgamma(y_n + 1)] + sum_d [b_d^2 / 2 + log(2 pi) / 2]
+//   dU/db = X^T (mu - y) + b,      eta = X b + o,  mu = exp(eta)
+//
+// Its side slot holds y (entries 0..31) and the offset (32..63) in one row permutation; rows >= n_rows
+// have y = 0 and the offset -inf, so mu = 0 exactly and the residual and the U term vanish without a
+// select.  The kernel accumulates sum mu; sum_n y_n eta_n = <X^T y, b> + sum_n y_n o_n, and with
+// sum_n lgamma(y_n + 1) that is the X^T y table plus ONE float64 scalar of the pack.  D <= 64 runs
+// the 4 x 1 class with DTS = 1 or 2 (instantiated for this policy only).  A chain whose eta passes
+// float32's exp range gets mu = +inf in its own B-operand column: U = +inf (the float64 parts are
+// finite), and no other chain changes by a bit.
 #include <math.h>
 #include <stdlib.h>
 
@@ -65,12 +81,12 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 constexpr int LW_ROWS = 32;
-constexpr int LW_MIN_D = 65, LW_MAX_D = 1024;
+constexpr int LW_MAX_D = 1024;
 constexpr int LW_CHUNK = 6 * 1024;  // six pieces
 constexpr int LW_LABEL_BYTES = 256;
 
-// packed buffer: X^T y as float64[1024] | the tiles
-constexpr size_t LW_TILE_OFFSET = (size_t)LW_MAX_D * sizeof(double);
+// packed buffer: X^T y as float64[1024] | the policy's head (LK::HEAD_BYTES) | the tiles
+constexpr size_t LW_XTY_BYTES = (size_t)LW_MAX_D * sizeof(double);
 
 // Shape class of D: CT chain tiles x DS feature slices of DTS d-tiles (32 features) each, and the
 // ring depth R.  D <= 128 runs 4 x 1 (no exchange: the slice is the whole row), not 4 x 2 with
@@ -81,7 +97,7 @@ struct lw_shape {
 inline lw_shape lw_class(int D) {
   const int DS = D <= 128 ? 1 : D <= 256 ? 2 : D <= 512 ? 4 : 8;
   const int CT = D <= 256 ? 4 : D <= 512 ? 2 : 1;
-  const int DTS = (D + 32 * DS - 1) / (32 * DS);  // 3 or 4 for 65 <= D <= 1024
+  const int DTS = (D + 32 * DS - 1) / (32 * DS);  // 3 or 4 for 65 <= D <= 1024, 1 or 2 below
   return {CT, DS, DTS};
 }
 inline size_t lw_tile_bytes(int D) {
@@ -123,6 +139,31 @@ __global__ __launch_bounds__(CS_THREADS) void k_logreg_wide_colsums(const float*
   }
 }
 
+// Poisson pack: head[0] = sum_n lgamma(y_n + 1) - sum_n y_n o_n in float64 (one workgroup, the same
+// fixed tree), and the first row whose count is negative, not whole or >= 2^24 (`bad` starts at ~0)
+__global__ void k_poisson_bad_reset(unsigned long long* bad) { *bad = ~0ull; }
+__global__ __launch_bounds__(CS_THREADS) void k_poisson_const(const float* __restrict__ y,
+                                                              const float* __restrict__ off, int64_t n,
+                                                              double* __restrict__ head, unsigned long long* bad) {
+  __shared__ double red[CS_THREADS];
+  double acc = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += CS_THREADS) {
+    const float v = y[i];
+    if (!(v >= 0.0f) || v != floorf(v) || v >= 16777216.0f) {
+      atomicMin(bad, (unsigned long long)i);
+      continue;
+    }
+    acc += lgamma((double)v + 1.0) - (off ? (double)v * (double)off[i] : 0.0);
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int k = CS_THREADS / 2; k > 0; k >>= 1) {
+    if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) head[0] = red[0];
+}
+
 // Packed tile = DS slices x 2 DTS chunks x 6 pieces of 1 KiB, each piece a 64-lane x 16-byte
 // operand fragment in lane order (lane (r, h), elements j = 0..7), then the labels.  Slice i covers
 // the features d0 = 32 DTS i ..:
@@ -131,11 +172,14 @@ __global__ __launch_bounds__(CS_THREADS) void k_logreg_wide_colsums(const float*
 //   chunk DTS + dt, piece 2 p + s     GEMM2 A = X^T[32 cols][16 rows], plane p, d-tile dt, k-step s:
 //                                     X[16 s + 8 (j >> 2) + 4 h + (j & 3)][d0 + 32 dt + r] -- the k
 //                                     order of the GEMM1 accumulator used as the B operand
-//   labels: float[64], entry 16 h + i = y of row (i & 3) + 8 (i >> 2) + 4 h, -1 for rows >= n
-//           (entries 32.. are zero)
+//   side slot: float[64], LK::side_entry: entry 16 h + i belongs to row (i & 3) + 8 (i >> 2) + 4 h
+//           Bernoulli: y, -1 for rows >= n (entries 32.. are zero)
+//           Poisson:   y, 0 for rows >= n; entry 32 + 16 h + i the row's offset, -inf for rows >= n
 // Rows >= n_rows and features >= D are zero.  One thread per 16 bytes.
-__global__ void k_logreg_wide_pack(const float* __restrict__ X, const float* __restrict__ y, int64_t n, int D, int DS,
-                                   int DTS, int64_t ntiles, char* __restrict__ out) {
+template <class LK>
+__global__ void k_logreg_wide_pack(const float* __restrict__ X, const float* __restrict__ y,
+                                   const float* __restrict__ off, int64_t n, int D, int DS, int DTS, int64_t ntiles,
+                                   char* __restrict__ out) {
   const int NP = DS * 12 * DTS;                    // pieces of a tile
   const int64_t per = (int64_t)NP * 64 + LW_LABEL_BYTES / 16;  // 16-byte items of a tile
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -145,15 +189,15 @@ __global__ void k_logreg_wide_pack(const float* __restrict__ X, const float* __r
   const int64_t r0 = t * LW_ROWS;
   char* dst = out + (size_t)t * ((size_t)NP * 1024 + LW_LABEL_BYTES) + (size_t)item * 16;
   if (item >= NP * 64) {
-    const int q = item - NP * 64;  // labels 4 q .. 4 q + 3
+    const int q = item - NP * 64;  // entries 4 q .. 4 q + 3
     f32x4 f = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (q < 8) {
-      const int hh = q >> 2;
+    if (q < LK::SIDE_QUADS) {
+      const int hh = (q >> 2) & 1;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int ii = 4 * (q & 3) + k;
         const int64_t row = r0 + (ii & 3) + 8 * (ii >> 2) + 4 * hh;
-        f[k] = row < n ? y[row] : -1.0f;
+        f[k] = LK::side_entry(y, off, row, n, q >= 8);
       }
     }
     *reinterpret_cast<f32x4*>(dst) = f;
@@ -250,6 +294,58 @@ __device__ __forceinline__ void lw_epilogue(const nmx_f32x16& acc, const f32x4 (
   }
 }
 
+// Poisson epilogue: mu = exp(l + o) as one exp2, res = mu - y formed here, per row, so the
+// cancellation near the mode happens before the bf16 split; U term mu.  A masked row has o = -inf
+// and y = 0: mu = 0 exactly.  The relative error of mu is the absolute error of l + o (f32-accurate
+// split-bf16 logit, one rounding of the sum, one of the product with log2 e: about |eta| 2^-23), the
+// same budget as a float32 evaluation of exp(eta).
+// `acc` is eta: the kernel has added the offsets.
+template <bool ACC>
+__device__ __forceinline__ void lw_epilogue_poisson(const nmx_f32x16& acc, const f32x4 (&y4)[4], float (&res)[16],
+                                                    double& pe) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float mu = __builtin_amdgcn_exp2f(acc[r] * LOG2E);
+    res[r] = mu - y4[r >> 2][r & 3];
+    if constexpr (ACC) pe += (double)mu;
+  }
+}
+
+// The likelihood policies: the widths served, the bytes between the X^T y table and the tiles, what
+// the pack puts into the side slot, and the epilogue.
+struct lk_bernoulli {
+  static constexpr int MIN_D = 65;
+  static constexpr size_t HEAD_BYTES = 0;
+  static constexpr int SIDE_QUADS = 8;      // 16-byte items of the side slot that hold data
+  static constexpr bool HAS_OFFSET = false;  // entries 32..63 of the side slot are added to the logits
+  static constexpr const char* NAME = "logreg_wide";
+  static __device__ __forceinline__ float side_entry(const float* y, const float*, int64_t row, int64_t n, bool) {
+    return row < n ? y[row] : -1.0f;
+  }
+  template <bool ACC>
+  static __device__ __forceinline__ void epilogue(const nmx_f32x16& acc, const f32x4 (&y4)[4], float (&res)[16],
+                                                  double& pe) {
+    lw_epilogue<ACC>(acc, y4, res, pe);
+  }
+};
+struct lk_poisson {
+  static constexpr int MIN_D = 1;
+  static constexpr size_t HEAD_BYTES = 256;  // float64 constant of U | the bad-count slot
+  static constexpr int SIDE_QUADS = 16;
+  static constexpr bool HAS_OFFSET = true;
+  static constexpr const char* NAME = "poisson";
+  static __device__ __forceinline__ float side_entry(const float* y, const float* off, int64_t row, int64_t n,
+                                                     bool second) {
+    if (!second) return row < n ? y[row] : 0.0f;
+    return row < n ? (off ? off[row] : 0.0f) : -INFINITY;
+  }
+  template <bool ACC>
+  static __device__ __forceinline__ void epilogue(const nmx_f32x16& acc, const f32x4 (&y4)[4], float (&res)[16],
+                                                  double& pe) {
+    lw_epilogue_poisson<ACC>(acc, y4, res, pe);
+  }
+};
+
 template <int CT, int DS, int DTS, int R>
 struct lw_cfg {
   static constexpr int WAVES = CT * DS, NCH = 2 * DTS, KBS = 2 * DTS, DW = 32 * DTS;
@@ -266,7 +362,7 @@ struct lw_cfg {
   static_assert(LDS_BYTES <= 160 * 1024, "the CU's LDS");
 };
 
-template <int CT, int DS, int DTS, int R>
+template <class LK, int CT, int DS, int DTS, int R>
 __global__ __launch_bounds__(64 * CT * DS) void k_logreg_wide(const char* __restrict__ Xq, int64_t ntiles, int D,
                                                               int S, int Gt, nmx_eval_batch ev,
                                                               float* __restrict__ gpart,
@@ -439,14 +535,27 @@ __global__ __launch_bounds__(64 * CT * DS) void k_logreg_wide(const char* __rest
         }
         f32x4 y4[4];
         const unsigned la = lw_lds_addr(lab + (kt & 1) * LW_LABEL_BYTES) + 64 * h;
+        if constexpr (LK::HAS_OFFSET) {
+          // the slot's second half joins the accumulator first, so that its four registers are free
+          // again before the first half is read (a round trip to LDS per tile, against 12 DW MFMAs)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) lw_lds_read(y4[k], la + LW_LABEL_BYTES / 2 + 16 * k);
+          lw_lds_wait();
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            lw_pin(y4[k]);
+#pragma unroll
+            for (int m = 0; m < 4; ++m) acc[4 * k + m] += y4[k][m];
+          }
+        }
 #pragma unroll
         for (int k = 0; k < 4; ++k) lw_lds_read(y4[k], la + 16 * k);
         lw_lds_wait();
 #pragma unroll
         for (int k = 0; k < 4; ++k) lw_pin(y4[k]);
         float res[16];
-        if (sl == 0) lw_epilogue<true>(acc, y4, res, pe);
-        else lw_epilogue<false>(acc, y4, res, pe);
+        if (sl == 0) LK::template epilogue<true>(acc, y4, res, pe);
+        else LK::template epilogue<false>(acc, y4, res, pe);
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
           float v[8];
@@ -496,8 +605,10 @@ __global__ __launch_bounds__(64 * CT * DS) void k_logreg_wide(const char* __rest
 
 // One workgroup per (64 batch positions, coordinate j or the U row j = D).  Wave w sums the slabs
 // [w S / 4, (w + 1) S / 4) in order -- and, on the U row, its quarter of the coordinates'
-// z^2 / 2 - xty z in float64 -- then the four wave sums are added in wave order.
+// z^2 / 2 - xty z in float64 -- then the four wave sums are added in wave order.  A policy with a
+// head adds its float64 constant (xty[LW_MAX_D]) once per chain, last.
 constexpr int FIN_WAVES = 4;
+template <class LK>
 __global__ __launch_bounds__(64 * FIN_WAVES) void k_logreg_wide_finalize(const float* __restrict__ gpart,
                                                                          const double* __restrict__ pepart, int S,
                                                                          int D, nmx_eval_batch ev,
@@ -539,65 +650,79 @@ __global__ __launch_bounds__(64 * FIN_WAVES) void k_logreg_wide_finalize(const f
     double s = 0.0;
 #pragma unroll
     for (int i = 0; i < FIN_WAVES; ++i) s += part[i][lane];
-    ev.pe[c] = (float)(s + 0.9189385332046727 * D);
+    s += 0.9189385332046727 * D;
+    if constexpr (LK::HEAD_BYTES > 0) s += xty[LW_MAX_D];
+    ev.pe[c] = (float)s;
   }
 }
 
-bool lw_shape_ok(int64_t n_rows, int dim) { return n_rows > 0 && dim >= LW_MIN_D && dim <= LW_MAX_D; }
+bool lw_shape_ok(int64_t n_rows, int dim, int min_d) { return n_rows > 0 && dim >= min_d && dim <= LW_MAX_D; }
 
-int lw_check_shape(const char* what, int64_t n_rows, int dim) {
+int lw_check_shape(const char* name, const char* fn, int64_t n_rows, int dim, int min_d) {
   if (n_rows <= 0)
-    return nmx_fail(NMX_ERR_INVALID, "%s: need n_rows >= 1 (got n_rows = %lld)", what, (long long)n_rows);
-  if (dim < LW_MIN_D || dim > LW_MAX_D)
-    return nmx_fail(NMX_ERR_INVALID, "%s: need %d <= dim <= %d (got dim = %d)", what, LW_MIN_D, LW_MAX_D, dim);
+    return nmx_fail(NMX_ERR_INVALID, "%s_%s: need n_rows >= 1 (got n_rows = %lld)", name, fn, (long long)n_rows);
+  if (dim < min_d || dim > LW_MAX_D)
+    return nmx_fail(NMX_ERR_INVALID, "%s_%s: need %d <= dim <= %d (got dim = %d)", name, fn, min_d, LW_MAX_D, dim);
   // a split's tiles are addressed by 32-bit byte offsets
   const int64_t per = lw_ntiles(n_rows) / lw_num_splits(n_rows, dim) + 1;
   if (per * (int64_t)lw_tile_bytes(dim) >= (int64_t)1 << 31)
-    return nmx_fail(NMX_ERR_INVALID, "%s: n_rows = %lld is past the kernel's 2 GiB of tiles per row split", what,
+    return nmx_fail(NMX_ERR_INVALID, "%s_%s: n_rows = %lld is past the kernel's 2 GiB of tiles per row split", name, fn,
                     (long long)n_rows);
   return NMX_OK;
 }
 
-template <int CT, int DS, int DTS, int R>
-int lw_launch(dim3 grid, hipStream_t s, const char* Xq, int64_t nt, int D, int S, int Gt, const nmx_eval_batch& ev,
-              float* gpart, double* pepart) {
+struct lw_args {
+  dim3 grid;
+  hipStream_t s;
+  const char* Xq;
+  int64_t nt;
+  int D, S, Gt;
+  const nmx_eval_batch& ev;
+  float* gpart;
+  double* pepart;
+};
+template <class LK, int CT, int DS, int DTS, int R>
+int lw_launch(const lw_args& a) {
   using C = lw_cfg<CT, DS, DTS, R>;
-  if (int st = nmx_lds_limit((const void*)k_logreg_wide<CT, DS, DTS, R>, C::LDS_BYTES, s, "k_logreg_wide")) return st;
-  hipLaunchKernelGGL((k_logreg_wide<CT, DS, DTS, R>), grid, dim3(64 * C::WAVES), C::LDS_BYTES, s, Xq, nt, D, S, Gt, ev,
-                     gpart, pepart);
+  if (int st = nmx_lds_limit((const void*)k_logreg_wide<LK, CT, DS, DTS, R>, C::LDS_BYTES, a.s, "k_logreg_wide"))
+    return st;
+  hipLaunchKernelGGL((k_logreg_wide<LK, CT, DS, DTS, R>), a.grid, dim3(64 * C::WAVES), C::LDS_BYTES, a.s, a.Xq, a.nt, a.D,
+                     a.S, a.Gt, a.ev, a.gpart, a.pepart);
   return NMX_OK;
 }
-template <int CT, int DS, int R>
-int lw_launch_dts(int DTS, dim3 grid, hipStream_t s, const char* Xq, int64_t nt, int D, int S, int Gt,
-                  const nmx_eval_batch& ev, float* gpart, double* pepart) {
-  if (DTS == 3) return lw_launch<CT, DS, 3, R>(grid, s, Xq, nt, D, S, Gt, ev, gpart, pepart);
-  return lw_launch<CT, DS, 4, R>(grid, s, Xq, nt, D, S, Gt, ev, gpart, pepart);
+// DTS = 3 or 4 from 65 features on; 1 or 2 below, in the 4 x 1 class of a policy that serves them
+template <class LK, int CT, int DS, int R>
+int lw_launch_dts(int DTS, const lw_args& a) {
+  if constexpr (LK::MIN_D <= 64 && DS == 1) {
+    if (DTS == 1) return lw_launch<LK, CT, DS, 1, R>(a);
+    if (DTS == 2) return lw_launch<LK, CT, DS, 2, R>(a);
+  }
+  if (DTS == 3) return lw_launch<LK, CT, DS, 3, R>(a);
+  return lw_launch<LK, CT, DS, 4, R>(a);
 }
 
-}  // namespace
-
-extern "C" size_t nmx_logreg_wide_packed_bytes(int64_t n_rows, int dim) {
-  if (!lw_shape_ok(n_rows, dim)) return 0;
-  return LW_TILE_OFFSET + (size_t)lw_ntiles(n_rows) * lw_tile_bytes(dim);
+// The four entry points of a policy.
+template <class LK>
+size_t lw_packed_bytes(int64_t n_rows, int dim) {
+  if (!lw_shape_ok(n_rows, dim, LK::MIN_D)) return 0;
+  return LW_XTY_BYTES + LK::HEAD_BYTES + (size_t)lw_ntiles(n_rows) * lw_tile_bytes(dim);
 }
 
-extern "C" int nmx_logreg_wide_pack(const float* X, const float* y, int64_t n_rows, int dim, void* packed,
-                                    void* stream) {
-  if (int st = lw_check_shape("logreg_wide_pack", n_rows, dim)) return st;
-  if (!X || !y || !packed) return nmx_fail(NMX_ERR_INVALID, "logreg_wide_pack: NULL pointer");
-  hipStream_t s = (hipStream_t)stream;
+template <class LK>
+int lw_pack(const float* X, const float* y, const float* off, int64_t n_rows, int dim, void* packed, hipStream_t s) {
   hipLaunchKernelGGL(k_logreg_wide_colsums, dim3(dim), dim3(CS_THREADS), 0, s, X, y, n_rows, dim, (double*)packed);
   if (int st = nmx_check_launch("k_logreg_wide_colsums")) return st;
   const lw_shape c = lw_class(dim);
   const int64_t nt = lw_ntiles(n_rows);
   const int64_t nthreads = nt * (int64_t)(lw_tile_bytes(dim) / 16);
-  hipLaunchKernelGGL(k_logreg_wide_pack, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, s, X, y, n_rows, dim,
-                     c.DS, c.DTS, nt, (char*)packed + LW_TILE_OFFSET);
+  hipLaunchKernelGGL(k_logreg_wide_pack<LK>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, s, X, y, off,
+                     n_rows, dim, c.DS, c.DTS, nt, (char*)packed + LW_XTY_BYTES + LK::HEAD_BYTES);
   return nmx_check_launch("k_logreg_wide_pack");
 }
 
-extern "C" size_t nmx_logreg_wide_workspace_bytes(int64_t n_rows, int dim, int num_chains) {
-  if (!lw_shape_ok(n_rows, dim) || num_chains <= 0) return 0;
+template <class LK>
+size_t lw_workspace_bytes(int64_t n_rows, int dim, int num_chains) {
+  if (!lw_shape_ok(n_rows, dim, LK::MIN_D) || num_chains <= 0) return 0;
   const size_t ldc = (size_t)(num_chains + 63) / 64 * 64;
   const size_t S = lw_num_splits(n_rows, dim);
   const size_t g = S * dim * ldc * sizeof(float);
@@ -605,32 +730,84 @@ extern "C" size_t nmx_logreg_wide_workspace_bytes(int64_t n_rows, int dim, int n
   return (g + 255) / 256 * 256 + p;
 }
 
-extern "C" int nmx_logreg_wide_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch* ev,
-                                       void* workspace, void* stream) {
-  if (int st = lw_check_shape("logreg_wide_pe_grad", n_rows, dim)) return st;
+template <class LK>
+int lw_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch* ev, void* workspace, void* stream) {
+  if (int st = lw_check_shape(LK::NAME, "pe_grad", n_rows, dim, LK::MIN_D)) return st;
   if (!ev || !ev->z || !ev->grad || !ev->pe)
-    return nmx_fail(NMX_ERR_INVALID, "logreg_wide_pe_grad: eval batch has NULL pointers");
+    return nmx_fail(NMX_ERR_INVALID, "%s_pe_grad: eval batch has NULL pointers", LK::NAME);
   if (ev->num_chains <= 0 || ev->ldc < ev->num_chains || ev->ldc % 64)
-    return nmx_fail(NMX_ERR_INVALID, "logreg_wide_pe_grad: bad num_chains/ldc (%d/%d)", ev->num_chains, ev->ldc);
-  if (!packed || !workspace) return nmx_fail(NMX_ERR_INVALID, "logreg_wide_pe_grad: NULL packed/workspace");
+    return nmx_fail(NMX_ERR_INVALID, "%s_pe_grad: bad num_chains/ldc (%d/%d)", LK::NAME, ev->num_chains, ev->ldc);
+  if (!packed || !workspace) return nmx_fail(NMX_ERR_INVALID, "%s_pe_grad: NULL packed/workspace", LK::NAME);
   hipStream_t s = (hipStream_t)stream;
   const int S = lw_num_splits(n_rows, dim);
   float* gpart = (float*)workspace;
   double* pepart = (double*)((char*)workspace + ((size_t)S * dim * ev->ldc * sizeof(float) + 255) / 256 * 256);
-  const int64_t nt = lw_ntiles(n_rows);
   const lw_shape c = lw_class(dim);
-  const char* Xq = (const char*)packed + LW_TILE_OFFSET;
   const int nb = std::min(ev->num_chains, ev->ldc);  // batch positions that can hold a chain
   const int Gt = (nb + 32 * c.CT - 1) / (32 * c.CT);
-  const dim3 grid((unsigned)Gt * S);
+  const lw_args a = {dim3((unsigned)Gt * S), s,  (const char*)packed + LW_XTY_BYTES + LK::HEAD_BYTES,
+                     lw_ntiles(n_rows),      dim, S, Gt, *ev, gpart, pepart};
   int st;
-  if (c.DS == 1) st = lw_launch_dts<4, 1, 3>(c.DTS, grid, s, Xq, nt, dim, S, Gt, *ev, gpart, pepart);
-  else if (c.DS == 2) st = lw_launch_dts<4, 2, 3>(c.DTS, grid, s, Xq, nt, dim, S, Gt, *ev, gpart, pepart);
-  else if (c.DS == 4) st = lw_launch_dts<2, 4, 3>(c.DTS, grid, s, Xq, nt, dim, S, Gt, *ev, gpart, pepart);
-  else st = lw_launch_dts<1, 8, 2>(c.DTS, grid, s, Xq, nt, dim, S, Gt, *ev, gpart, pepart);
+  if (c.DS == 1) st = lw_launch_dts<LK, 4, 1, 3>(c.DTS, a);
+  else if (c.DS == 2) st = lw_launch_dts<LK, 4, 2, 3>(c.DTS, a);
+  else if (c.DS == 4) st = lw_launch_dts<LK, 2, 4, 3>(c.DTS, a);
+  else st = lw_launch_dts<LK, 1, 8, 2>(c.DTS, a);
   if (st) return st;
   if (int e = nmx_check_launch("k_logreg_wide")) return e;
-  hipLaunchKernelGGL(k_logreg_wide_finalize, dim3((nb + 63) / 64, dim + 1), dim3(64 * FIN_WAVES), 0, s, gpart, pepart,
-                     S, dim, *ev, (const double*)packed);
+  hipLaunchKernelGGL(k_logreg_wide_finalize<LK>, dim3((nb + 63) / 64, dim + 1), dim3(64 * FIN_WAVES), 0, s, gpart,
+                     pepart, S, dim, *ev, (const double*)packed);
   return nmx_check_launch("k_logreg_wide_finalize");
+}
+
+}  // namespace
+
+extern "C" size_t nmx_logreg_wide_packed_bytes(int64_t n_rows, int dim) {
+  return lw_packed_bytes<lk_bernoulli>(n_rows, dim);
+}
+
+extern "C" int nmx_logreg_wide_pack(const float* X, const float* y, int64_t n_rows, int dim, void* packed,
+                                    void* stream) {
+  if (int st = lw_check_shape("logreg_wide", "pack", n_rows, dim, lk_bernoulli::MIN_D)) return st;
+  if (!X || !y || !packed) return nmx_fail(NMX_ERR_INVALID, "logreg_wide_pack: NULL pointer");
+  return lw_pack<lk_bernoulli>(X, y, nullptr, n_rows, dim, packed, (hipStream_t)stream);
+}
+
+extern "C" size_t nmx_logreg_wide_workspace_bytes(int64_t n_rows, int dim, int num_chains) {
+  return lw_workspace_bytes<lk_bernoulli>(n_rows, dim, num_chains);
+}
+
+extern "C" int nmx_logreg_wide_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch* ev,
+                                       void* workspace, void* stream) {
+  return lw_pe_grad<lk_bernoulli>(packed, n_rows, dim, ev, workspace, stream);
+}
+
+extern "C" size_t nmx_poisson_packed_bytes(int64_t n_rows, int dim) { return lw_packed_bytes<lk_poisson>(n_rows, dim); }
+
+// Synchronises the stream once, to refuse a bad count before anything is packed.
+extern "C" int nmx_poisson_pack(const float* X, const float* y, const float* offset, int64_t n_rows, int dim,
+                                void* packed, void* stream) {
+  if (int st = lw_check_shape("poisson", "pack", n_rows, dim, lk_poisson::MIN_D)) return st;
+  if (!X || !y || !packed) return nmx_fail(NMX_ERR_INVALID, "poisson_pack: NULL pointer");
+  hipStream_t s = (hipStream_t)stream;
+  double* head = (double*)((char*)packed + LW_XTY_BYTES);
+  unsigned long long* bad = (unsigned long long*)(head + 1);
+  hipLaunchKernelGGL(k_poisson_bad_reset, dim3(1), dim3(1), 0, s, bad);
+  hipLaunchKernelGGL(k_poisson_const, dim3(1), dim3(CS_THREADS), 0, s, y, offset, n_rows, head, bad);
+  if (int st = nmx_check_launch("k_poisson_const")) return st;
+  unsigned long long first = 0;
+  if (hipMemcpyAsync(&first, bad, sizeof(first), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return nmx_fail(NMX_ERR_HIP, "poisson_pack: reading the count check back failed");
+  if (first != ~0ull)
+    return nmx_fail(NMX_ERR_INVALID, "poisson_pack: the count of row %llu is not a whole number in [0, 2^24)", first);
+  return lw_pack<lk_poisson>(X, y, offset, n_rows, dim, packed, s);
+}
+
+extern "C" size_t nmx_poisson_workspace_bytes(int64_t n_rows, int dim, int num_chains) {
+  return lw_workspace_bytes<lk_poisson>(n_rows, dim, num_chains);
+}
+
+extern "C" int nmx_poisson_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch* ev,
+                                   void* workspace, void* stream) {
+  return lw_pe_grad<lk_poisson>(packed, n_rows, dim, ev, workspace, stream);
 }

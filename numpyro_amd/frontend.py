@@ -9,8 +9,8 @@ differentiates it with JAX.  Here the trace records each site's distribution, pa
 observed data; a matcher per supported structure checks the priors' constants and the
 likelihood's expression and returns the bound fused potential, with the model's own site
 names.  Supported structures: the reference's examples on the hot path (covtype logistic
-regression and its multi-class form, softmax regression; eight schools, funnel and its
-LocScaleReparam(0) form, stochastic volatility, the BNN) and the test targets (diagonal normal, multivariate normal).  For anything else
+regression, its multi-class form, softmax regression, and Poisson regression; eight schools,
+funnel and its LocScaleReparam(0) form, stochastic volatility, the BNN) and the test targets (diagonal normal, multivariate normal).  For anything else
 potential_from_model raises NotImplementedError naming the traced sites; NUTS / HMC then hand
 the model to the program compiler (numpyro_amd/program.py compile_model), which lowers the
 traced log-joint to a straight-line program of primitive operations evaluated, with its
@@ -157,6 +157,35 @@ def _match_logistic(trace):
     if not (isinstance(lg, Sym) and lg.op == "matmul" and _const(lg.args[0]) and _latent(lg.args[1], lat[0].name)):
         return None
     return _renamed(P.LogisticRegression(lg.args[0], o.obs), {"coefs": lat[0].name})
+
+
+def _match_poisson(trace):
+    """coefs ~ Normal(0, 1)^D, obs ~ Poisson(exp(X @ coefs)) or Poisson(exp(X @ coefs + offset)) with a
+    constant [N] offset on either side of the sum; whole counts in [0, 2^24), D <= 1024."""
+    lat, obs = _split(trace)
+    if len(lat) != 1 or len(obs) != 1 or not _std_normal(lat[0]) or len(lat[0].shape) != 1:
+        return None
+    o = obs[0]
+    if not _is(o.fn, dist.Poisson):
+        return None
+    rate = _base(o.fn).rate
+    if not (isinstance(rate, Sym) and rate.op == "exp"):
+        return None
+    eta, offset = rate.args[0], None
+    if isinstance(eta, Sym) and eta.op == "add":
+        a, b = eta.args
+        eta, offset = (a, b) if isinstance(a, Sym) else (b, a)
+    if not (isinstance(eta, Sym) and eta.op == "matmul" and _const(eta.args[0]) and _latent(eta.args[1], lat[0].name)):
+        return None
+    X = eta.args[0]
+    N, D = (tuple(shape_of(X)) + (0, 0))[:2]
+    if len(shape_of(X)) != 2 or D != lat[0].shape[0] or D > P.PoissonRegression.MAX_FEATURES:
+        return None
+    if offset is not None and not (_const(offset) and tuple(shape_of(offset)) == (N,)):
+        return None
+    if tuple(shape_of(o.obs)) != (N,) or not P.poisson_counts_ok(o.obs):
+        return None
+    return _renamed(P.PoissonRegression(X, o.obs, offset), {"coefs": lat[0].name})
 
 
 def softmax_structure(trace):
@@ -334,7 +363,8 @@ def _match_normal(trace):
     return None
 
 
-MATCHERS = (_match_logistic, _match_softmax, _match_eight_schools, _match_funnel, _match_sv, _match_bnn, _match_normal)
+MATCHERS = (_match_logistic, _match_poisson, _match_softmax, _match_eight_schools, _match_funnel, _match_sv, _match_bnn,
+            _match_normal)
 
 
 def potential_from_model(model, args=(), kwargs=None):
@@ -348,7 +378,7 @@ def potential_from_model(model, args=(), kwargs=None):
             return _with_traced_deterministics(pot, trace)
     raise NotImplementedError(
         "no fused kernel for this model structure (sites: " + ", ".join(map(repr, trace.sites.values())) +
-        "); supported: the reference's covtype logistic regression, softmax regression, eight schools, funnel (+ LocScaleReparam), "
+        "); supported: the reference's covtype logistic regression, softmax regression, Poisson regression, eight schools, funnel (+ LocScaleReparam), "
         "stochastic volatility and BNN examples, and diagonal / multivariate normal targets")
 
 

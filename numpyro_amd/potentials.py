@@ -242,6 +242,65 @@ class LogisticRegression(Potential):
         return 4.0 * self.N * self.dim * num_chains
 
 
+def poisson_counts_ok(counts):
+    """The counts the fused Poisson kernel takes: whole numbers in [0, 2^24), exact in float32."""
+    y = counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)
+    return y.dtype.kind in "iuf" and bool(np.all((y >= 0) & (y < 2 ** 24) & (y == np.floor(y))))
+
+
+class PoissonRegression(Potential):
+    """Count regression: coefs ~ N(0, 1)^D, obs ~ Poisson(exp(X @ coefs + offset)), 1 to 1024
+    features, on the D-blocked kernel of csrc/potential_logreg_wide.hip with the Poisson likelihood
+    policy (the ``nmx_poisson_*`` entry points).  ``offset`` is [N] (a log exposure) or None."""
+
+    MAX_FEATURES = 1024
+
+    def __init__(self, data, counts, offset=None):
+        self.X_in, self.y_in, self.o_in = data, counts, offset
+        shape, yshape = tuple(data.shape), tuple(getattr(counts, "shape", None) or np.shape(counts))
+        if len(shape) != 2 or yshape != shape[:1]:
+            raise ValueError(f"Poisson regression needs data [N, D] and counts [N] (got {shape}, {yshape})")
+        if offset is not None and tuple(getattr(offset, "shape", None) or np.shape(offset)) != yshape:
+            raise ValueError(f"Poisson regression needs an offset of shape {list(yshape)}")
+        self.N, self.dim = int(shape[0]), int(shape[1])
+        if not 1 <= self.dim <= self.MAX_FEATURES:
+            raise ValueError(f"the fused Poisson-regression kernel supports 1 to {self.MAX_FEATURES} features "
+                             f"(got {self.dim})")
+        if not poisson_counts_ok(counts):
+            raise ValueError("Poisson regression needs counts that are whole numbers in [0, 2^24)")
+        self.sites = [("coefs", (self.dim,), REAL)]
+        self.packed = None
+
+    slots = 4  # workspaces, as LogisticRegression
+
+    def _bind(self, C, ldc, device):
+        if self.packed is None or self.packed.device != device:
+            X, y = _dev(self.X_in, device), _dev(self.y_in, device)
+            o = None if self.o_in is None else _dev(self.o_in, device)
+            nb = lib().nmx_poisson_packed_bytes(self.N, self.dim)
+            self.packed = torch.empty(nb // 4, dtype=torch.float32, device=device)
+            with torch.cuda.device(device):
+                check(lib().nmx_poisson_pack(ptr(X), ptr(y), ptr(o), self.N, self.dim, ptr(self.packed),
+                                             native.stream_ptr()), "nmx_poisson_pack")
+            del X, y, o
+        wb = lib().nmx_poisson_workspace_bytes(self.N, self.dim, ldc)  # the slabs' rows are ldc wide
+        self.workspace = torch.empty(wb, dtype=torch.uint8, device=device)
+        self._more_ws = []  # slots 1.. (allocated on first use)
+
+    def evaluate(self, ev, stream, slot=0):
+        ws = self.workspace
+        if slot:
+            while len(self._more_ws) < slot:
+                self._more_ws.append(torch.empty_like(self.workspace))
+            ws = self._more_ws[slot - 1]
+        check(lib().nmx_poisson_pe_grad(ptr(self.packed), self.N, self.dim, ctypes.byref(ev), ptr(ws), stream),
+              "nmx_poisson_pe_grad")
+
+    def flops_per_eval(self, num_chains):
+        """Algorithmic FLOPs of one evaluation (two GEMMs): 4 N D C."""
+        return 4.0 * self.N * self.dim * num_chains
+
+
 class SoftmaxRegression(Potential):
     """Multinomial logistic regression: coefs ~ N(0, 1)^(D x K), obs ~ Categorical(logits=X @ coefs)
     with integer labels in [0, K) (csrc/potential_softmax.hip)."""
@@ -482,6 +541,10 @@ def _softmax_regression(data, labels, num_classes=None):
 softmax_regression = FusedModel(
     "softmax_regression", _softmax_regression,
     "coefs ~ Normal(0, 1) [D, K], obs ~ Categorical(logits=X @ coefs): model(data, labels, num_classes=None)")
+
+poisson_regression = FusedModel(
+    "poisson_regression", lambda data, counts, offset=None: PoissonRegression(data, counts, offset),
+    "coefs ~ Normal(0, 1) [D], obs ~ Poisson(exp(X @ coefs + offset)): model(data, counts, offset=None)")
 
 eight_schools = FusedModel(
     "eight_schools", lambda J, sigma, y=None: EightSchools(J, sigma, y),
