@@ -565,6 +565,44 @@ int nmx_softmax_loglik(const void* workspace, const int32_t* y, int64_t n_rows, 
 int nmx_softmax_predict(const void* workspace, int64_t n_rows, int dim, int num_classes, const float* W,
                         int num_samples, uint64_t seed, int32_t* out, int64_t ld, void* stream);
 
+/* Logistic and Poisson regression after sampling: the pointwise log-likelihood table and posterior
+ * predictive counts for posterior samples W [num_samples][dim] (get_samples()["coefs"]),
+ * X [n_rows][dim] and an optional offset [n_rows], any data of that shape, 1 <= dim <= 1024
+ * (csrc/predictive_glm.hip: a blocked sample-by-row GEMM on split-bf16 MFMA, samples on the M axis
+ * and rows on the N axis, 128 x 128 output blocks with a K-loop through a two-slot LDS ring, the
+ * likelihood applied to the accumulator registers; the table agrees with the potentials to float32
+ * accuracy).  eta[s][n] = X[n][:] . W[s][:] + offset[n]:
+ *   nmx_glm_loglik   NMX_GLM_BERNOULLI  out[s ld + n] = y eta - softplus(eta), y in {0, 1}
+ *                    NMX_GLM_POISSON    out[s ld + n] = y eta - exp(eta) - lgamma(y + 1); -inf
+ *                                       (never NaN) where exp(eta) passes float32's range
+ *   nmx_glm_predict  NMX_GLM_POISSON    out[s ld + n] = a count from Poisson(exp(eta)), drawn as the
+ *                    NMX_DRAW_POISSON op draws it from the Philox blocks of (seed, sample
+ *                    sample0 + s, site 0, row n): it depends on (seed, sample, row) only; -1 where
+ *                    the rate is at or above NMX_POISSON_MAX_RATE.  Bernoulli draws are
+ *                    nmx_predict_logreg's and are refused here.
+ * ld >= n_rows is the row stride of `out` in elements; nothing outside out[s][0 .. n_rows),
+ * s < num_samples, is written.  Non-finite coefficients give NaN in that sample's row only, and a
+ * sample's row does not depend on num_samples, its position or ld.  nmx_glm_predictive_pack splits
+ * X into bf16 planes in the kernel's fragment order, once per data set, with the rows' side data
+ * (y as floats, offset, lgamma(y + 1) from float64); y and offset may be NULL (zeros: a workspace
+ * packed without y serves draws only).  It synchronises the stream once and fails, naming the first
+ * such row, on a Bernoulli label other than 0 or 1 or a Poisson count that is negative, not whole or
+ * >= 2^24.  The workspace of nmx_glm_predictive_workspace_bytes (0 for a shape out of range) also
+ * holds the scratch into which each launch splits its W: a launch takes at most the max_samples the
+ * workspace was sized for, and launches that share a workspace share a stream.  n_rows >= 1,
+ * 1 <= dim <= 1024, a known family, num_samples >= 1, ld >= n_rows and, for draws, n_rows <= 2^24
+ * (the counter's element field); anything else is NMX_ERR_INVALID with the argument named, before
+ * any launch. */
+#define NMX_GLM_BERNOULLI 0
+#define NMX_GLM_POISSON 1
+size_t nmx_glm_predictive_workspace_bytes(int64_t n_rows, int dim, int max_samples);
+int nmx_glm_predictive_pack(const float* X, const float* y, const float* offset, int64_t n_rows, int dim, int family,
+                            void* workspace, void* stream);
+int nmx_glm_loglik(void* workspace, int64_t n_rows, int dim, int family, const float* W, int num_samples, float* out,
+                   int64_t ld, void* stream);
+int nmx_glm_predict(void* workspace, int64_t n_rows, int dim, int family, const float* W, int num_samples,
+                    int64_t sample0, uint64_t seed, int32_t* out, int64_t ld, void* stream);
+
 /* ---- dense mass matrix (hmc_util.py:1203-1220 dense matvecs, hmc.py:103-108 momentum,
  *      hmc_util.py:612-620 dense Welford finalize) ----
  * With inverse mass M^-1 = T T^T, NUTS with dense mass on z is NUTS with identity mass on

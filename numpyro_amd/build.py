@@ -49,7 +49,7 @@ COMMON_FLAGS = [
 #   models; the predictive draws' accept tests round like their NumPy restatement, and so do the
 #   log-likelihood program and the Welford / Chan merges of its pointwise reductions, and the
 #   PSIS kernel's log ratios and sums, and the SVI step's z = loc + scale * eps, gradient sums and
-#   optimiser): the
+#   optimiser; predictive_glm.hip inlines the same Poisson draw into its epilogue): the
 #   same device function is inlined into several kernels (the launched step, the persistent
 #   schedule, the sync / async schedules), and whether the backend fuses a * b + c into an FMA
 #   depends on each kernel's code generation -- with contraction off every kernel rounds every
@@ -63,6 +63,7 @@ FILE_FLAGS = {"potential_logreg.hip": ["-fno-slp-vectorize"],
               "potential_small.hip": ["-ffp-contract=off"],
               "potential_program.hip": ["-ffp-contract=off"],
               "predictive_program.hip": ["-ffp-contract=off"],
+              "predictive_glm.hip": ["-ffp-contract=off"],
               "loglik_program.hip": ["-ffp-contract=off"],
               "psis.hip": ["-ffp-contract=off"],
               "svi.hip": ["-ffp-contract=off"]}

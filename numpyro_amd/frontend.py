@@ -145,8 +145,9 @@ def _half(x):
 
 
 # ----------------------------------------------------------------------------- matchers
-def _match_logistic(trace):
-    """examples/covtype.py:66-71: coefs ~ Normal(0, 1)^D, obs ~ Bernoulli(logits=X @ coefs)."""
+def logistic_structure(trace):
+    """(coefs site, obs site, X, None) of examples/covtype.py:66-71: coefs ~ Normal(0, 1)^D,
+    obs ~ Bernoulli(logits=X @ coefs), or None."""
     lat, obs = _split(trace)
     if len(lat) != 1 or len(obs) != 1 or not _std_normal(lat[0]) or len(lat[0].shape) != 1:
         return None
@@ -156,12 +157,21 @@ def _match_logistic(trace):
     lg = _base(o.fn).logits
     if not (isinstance(lg, Sym) and lg.op == "matmul" and _const(lg.args[0]) and _latent(lg.args[1], lat[0].name)):
         return None
-    return _renamed(P.LogisticRegression(lg.args[0], o.obs), {"coefs": lat[0].name})
+    return lat[0], o, lg.args[0], None
 
 
-def _match_poisson(trace):
-    """coefs ~ Normal(0, 1)^D, obs ~ Poisson(exp(X @ coefs)) or Poisson(exp(X @ coefs + offset)) with a
-    constant [N] offset on either side of the sum; whole counts in [0, 2^24), D <= 1024."""
+def _match_logistic(trace):
+    hit = logistic_structure(trace)
+    if hit is None:
+        return None
+    w, o, X, _ = hit
+    return _renamed(P.LogisticRegression(X, o.obs), {"coefs": w.name})
+
+
+def poisson_structure(trace):
+    """(coefs site, obs site, X, offset or None) of coefs ~ Normal(0, 1)^D, obs ~ Poisson(exp(X @ coefs))
+    or Poisson(exp(X @ coefs + offset)) with a constant [N] offset on either side of the sum; whole
+    counts in [0, 2^24), D <= 1024; or None."""
     lat, obs = _split(trace)
     if len(lat) != 1 or len(obs) != 1 or not _std_normal(lat[0]) or len(lat[0].shape) != 1:
         return None
@@ -185,7 +195,15 @@ def _match_poisson(trace):
         return None
     if tuple(shape_of(o.obs)) != (N,) or not P.poisson_counts_ok(o.obs):
         return None
-    return _renamed(P.PoissonRegression(X, o.obs, offset), {"coefs": lat[0].name})
+    return lat[0], o, X, offset
+
+
+def _match_poisson(trace):
+    hit = poisson_structure(trace)
+    if hit is None:
+        return None
+    w, o, X, offset = hit
+    return _renamed(P.PoissonRegression(X, o.obs, offset), {"coefs": w.name})
 
 
 def softmax_structure(trace):

@@ -16,6 +16,9 @@ table.
 A model whose trace is the softmax regression of the fused potential (frontend._match_softmax) has a
 rank-2 latent the program compiler refuses: its table comes from the kernel of that structure
 (csrc/predictive_softmax.hip through ``_SoftmaxRun``), with the same chunks, shapes and dictionaries.
+A model whose trace is exactly the logistic or Poisson regression of the fused potentials (one
+Normal(0, 1) [D] latent, logits or log rate X @ coefs, D <= 1024) is a plain GEMM with a pointwise
+epilogue: its table comes from the blocked MFMA kernel csrc/predictive_glm.hip (``_GlmRun``).
 """
 from __future__ import annotations
 
@@ -27,7 +30,10 @@ import torch
 
 from .. import native
 from .. import potentials as P
-from ..frontend import _host, _match_softmax, softmax_structure, trace_model
+from ..frontend import _host, _match_softmax, logistic_structure, poisson_structure, softmax_structure, trace_model
+from ..glm_predictive import MAX_FEATURES as MAX_GLM_FEATURES
+from ..glm_predictive import GlmPredictive
+from ..jnp import shape_of
 from ..native import check, lib, ptr
 from ..pointwise import PointwiseReducer
 from ..softmax_predictive import SoftmaxPredictive
@@ -134,12 +140,61 @@ class _SoftmaxRun:
         self.kernel.log_likelihood(self.y, self.W[s0:s0 + m], out)
 
 
+class _GlmRun:
+    """The same chunks() / launch() over the blocked regression kernel (csrc/predictive_glm.hip) for a
+    logistic or Poisson regression: X is split once with y and the offset, a chunk of samples is one
+    call of GlmPredictive.log_likelihood."""
+
+    def __init__(self, family, W_site, obs_site, X, offset, flat, batch_shape, S, what):
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{what} needs a GPU (the {family}-regression table is a HIP kernel)")
+        self.device = dev = torch.device("cuda", torch.cuda.current_device())
+        self.batch_shape, self.S = batch_shape, S
+        self.W = flat[W_site.name].to(dev, torch.float32).contiguous()
+        self.kernel = GlmPredictive(X, dev, family, y=obs_site.obs, offset=offset, max_samples=min(S, 4096))
+        self.prog = _SoftmaxProgram(obs_site.name, self.kernel.N)
+        self.chunk = max(1, min(S, MAX_WORKSPACE_BYTES // (4 * self.kernel.N)))  # the chunk's table under the limit
+
+    chunks = _Run.chunks
+
+    def launch(self, s0, m, out):
+        """Samples [s0, s0 + m) into the rows of ``out`` [>= m, N]."""
+        self.kernel.log_likelihood(self.W[s0:s0 + m], out)
+
+
+def _glm_hit(trace, flat):
+    """(family, coefs site, obs site, X, offset) where the trace is the logistic regression that
+    frontend._match_logistic accepts (labels all 0 or 1) or the Poisson regression of
+    frontend._match_poisson, inside the kernel's 1024 features, without a reparam and with the latent
+    among the samples as [S, D]; None for every other model."""
+    if trace.reparam:
+        return None
+    for family, structure in (("bernoulli", logistic_structure), ("poisson", poisson_structure)):
+        hit = structure(trace)
+        if hit is None:
+            continue
+        w, o, X, offset = hit
+        shape, y = tuple(shape_of(X)), _host(o.obs)
+        if len(shape) != 2 or shape[0] < 1 or not 1 <= shape[1] <= MAX_GLM_FEATURES or w.shape != (shape[1],):
+            return None
+        if y.shape != shape[:1] or (family == "bernoulli" and not np.isin(y, (0, 1)).all()):
+            return None
+        if w.name not in flat or tuple(flat[w.name].shape[1:]) != (shape[1],):
+            return None
+        return family, w, o, X, offset
+    return None
+
+
 def _run(model, posterior_samples, args, kwargs, batch_ndims, what):
     """The run of a model's trace: the fused kernel where the trace is the softmax regression that
     frontend._match_softmax recognises (same structure, limits and labels in range; X and y any data
-    of that shape), the log-likelihood program for every other model."""
+    of that shape), the blocked regression kernel where it is the logistic or Poisson regression of
+    the fused potentials (_glm_hit), the log-likelihood program for every other model."""
     flat, batch_shape, S = _flatten(model, posterior_samples, batch_ndims, what)
     trace = trace_model(getattr(model, "_nmx_model", model), args, kwargs, getattr(model, "_nmx_reparam", None))
+    glm = _glm_hit(trace, flat)
+    if glm is not None:
+        return _GlmRun(*glm, flat, batch_shape, S, what)
     hit = softmax_structure(trace)
     if hit is None or trace.reparam or hit[0].name not in flat or _match_softmax(trace) is None:
         return _Run(model, posterior_samples, args, kwargs, batch_ndims, what)

@@ -15,7 +15,9 @@ with ``obs=`` does under the reference's Predictive.  Deterministic sites (the m
 reparam.py:140-142) are returned by default, as the reference's ``_predictive`` does
 (util.py:870-877), computed from the posterior samples.  Models: covtype logistic regression
 (``obs``), softmax regression (``obs``: class labels, csrc/predictive_softmax.hip; also for a model
-function of that structure, which the program path would refuse for its rank-2 latent), eight schools (``obs``), BNN (``Y``), stochastic volatility (``r``: its returns are
+function of that structure, which the program path would refuse for its rank-2 latent), Poisson
+regression (``obs``: counts from the blocked MFMA kernel csrc/predictive_glm.hip, 1 to 1024 features,
+an optional offset; -1 where the rate is at or above 2^24), eight schools (``obs``), BNN (``Y``), stochastic volatility (``r``: its returns are
 both the observation and the series length, examples/stochastic_volatility.py:57-65, so -- as in
 the reference -- the observed data come back), funnel and its LocScaleReparam form (no observed
 site: deterministic ``x`` and any ``return_sites``, as examples/funnel.py:84-87 uses it).  Out of
@@ -83,6 +85,17 @@ def _predict_softmax(samples, seed, device, data, labels=None, num_classes=None,
     return {site: SoftmaxPredictive(data, device).draw(samples[latent], seed)}
 
 
+def _predict_poisson(samples, seed, device, data, counts=None, offset=None):
+    """Counts of obs ~ Poisson(exp(X @ coefs + offset)) (csrc/predictive_glm.hip)."""
+    from ..glm_predictive import GlmPredictive
+
+    coefs = samples["coefs"]
+    if counts is not None:
+        return {"obs": _observed(counts, coefs.shape[0], device, torch.int32)}
+    kernel = GlmPredictive(data, device, "poisson", offset=offset, max_samples=min(coefs.shape[0], 4096))
+    return {"obs": kernel.draw(coefs, seed)}
+
+
 def _predict_eight_schools(samples, seed, device, J, sigma, y=None):
     theta = samples["theta"].reshape(-1, J).to(device, torch.float32).contiguous()
     if y is not None:
@@ -124,6 +137,7 @@ def _predict_none(samples, seed, device, *args, **kwargs):
 _PREDICTORS = {
     "logistic_regression": (("obs",), _predict_logreg),
     "softmax_regression": (("obs",), _predict_softmax),
+    "poisson_regression": (("obs",), _predict_poisson),
     "eight_schools": (("obs",), _predict_eight_schools),
     "bnn": (("Y",), _predict_bnn),
     "stochastic_volatility": (("r",), _predict_sv),
@@ -135,7 +149,7 @@ _PREDICTORS = {
 # models whose Predictive draws nothing on the device (no free observed site)
 _HOST_ONLY = {"stochastic_volatility", "funnel", "funnel_reparam"}
 # models without a deterministic site whose potential cannot be built without the observed data
-_NO_DETERMINISTIC = {"softmax_regression"}
+_NO_DETERMINISTIC = {"softmax_regression", "poisson_regression"}
 
 
 def common_batch_shape(shapes):

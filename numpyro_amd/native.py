@@ -144,6 +144,7 @@ BINOMIAL_MAX_STEPS = 96  # NMX_BINOMIAL_MAX_STEPS
 BINOMIAL_BTRS_MEAN = 10.0  # NMX_BINOMIAL_BTRS_MEAN
 BINOMIAL_MAX_COUNT = 1 << 24  # NMX_BINOMIAL_MAX_COUNT
 DRAW_MAX_ELEMENTS = 1 << 24  # the counter's element field
+GLM_FAMILY = {"bernoulli": 0, "poisson": 1}  # NMX_GLM_BERNOULLI, NMX_GLM_POISSON
 POINTWISE_MAX_SPLITS = 64  # NMX_POINTWISE_MAX_SPLITS
 POINTWISE_MIN_SPLIT_ROWS = 16  # NMX_POINTWISE_MIN_SPLIT_ROWS
 PSIS_MAX_TAIL = 8192  # NMX_PSIS_MAX_TAIL
@@ -255,6 +256,10 @@ SIGNATURES: dict[str, tuple] = {
     "nmx_softmax_predictive_pack": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp]),
     "nmx_softmax_loglik": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_vp, c_i64, c_vp]),
     "nmx_softmax_predict": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_int, c_u64, c_vp, c_i64, c_vp]),
+    "nmx_glm_predictive_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
+    "nmx_glm_predictive_pack": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp]),
+    "nmx_glm_loglik": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_int, c_vp, c_i64, c_vp]),
+    "nmx_glm_predict": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_int, c_i64, c_u64, c_vp, c_i64, c_vp]),
     "nmx_dense_padded_dim": (c_int, [c_int]),
     "nmx_gemm_chains": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
     "nmx_gemm_chains_workspace_bytes": (c_size, [c_int, c_int]),
