@@ -514,6 +514,29 @@ size_t nmx_poisson_workspace_bytes(int64_t n_rows, int dim, int num_chains);
 int nmx_poisson_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch* ev, void* workspace,
                         void* stream);
 
+/* Horseshoe-prior (sparse) regression on the same kernel, with the prior as a second compile-time
+ * policy (csrc/potential_logreg_wide.hip): lambdas ~ HalfCauchy(1)^D, tau ~ HalfCauchy(1),
+ * unscaled_betas ~ N(0,1)^D, betas = tau lambdas unscaled_betas, and obs ~ Bernoulli(logits = X @ betas)
+ * (likelihood = 0) or Poisson(exp(X @ betas + offset)) (likelihood = 1).  dim is the number of features
+ * D, 1 <= D <= 1024 for both likelihoods; the eval batch has 2 D + 1 unconstrained rows: ul[d] = log
+ * lambdas[d] (row d), ut = log tau (row D), z[d] = unscaled_betas[d] (row D + 1 + d).  With
+ * s[d] = exp(ut + ul[d]), beta[d] = s[d] z[d], L the likelihood's part of U above and G = dL/dbeta:
+ *   U        = L(beta) + sum_d [log(2 cosh ul[d]) + log(pi/2)] + log(2 cosh ut) + log(pi/2)
+ *              + sum_d [z[d]^2 / 2 + log(2 pi) / 2]
+ *   dU/dz[d] = s[d] G[d] + z[d],  dU/dul[d] = beta[d] G[d] + tanh(ul[d]),  dU/dut = sum_d beta[d] G[d] + tanh(ut)
+ * Arguments, packed image and count rules as nmx_poisson_* (the Bernoulli likelihood takes offset =
+ * NULL only); the workspace adds two float64 rows per block of coordinates.  Three launches: the tile
+ * kernel, a finalize per block of coordinates, and the tau row with U; sums over coordinates are
+ * float64 in an order fixed by D alone, so the determinism is that of nmx_logreg_wide_*.  A chain whose
+ * ut + ul[d] passes float32's exp range gets a non-finite U; no other chain of the launch changes by a
+ * bit. */
+size_t nmx_horseshoe_packed_bytes(int likelihood, int64_t n_rows, int dim);
+int nmx_horseshoe_pack(int likelihood, const float* X, const float* y, const float* offset, int64_t n_rows, int dim,
+                       void* packed, void* stream);
+size_t nmx_horseshoe_workspace_bytes(int likelihood, int64_t n_rows, int dim, int num_chains);
+int nmx_horseshoe_pe_grad(int likelihood, const void* packed, int64_t n_rows, int dim, const nmx_eval_batch* ev,
+                          void* workspace, void* stream);
+
 /* Softmax (multinomial logistic) regression: coefs ~ N(0,1)^(D x K),
  * obs ~ Categorical(logits = X @ coefs), coordinate of coefs[d][k] = d K + k (ravel order):
  *   U(W)  = sum_n [logsumexp_k l_nk - l_{n, y_n}] + sum_dk [W_dk^2 / 2 + log(2 pi) / 2],  l = X W

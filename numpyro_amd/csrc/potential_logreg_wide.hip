@@ -62,9 +62,42 @@
 // have y = 0 and the offset -inf, so mu = 0 exactly and the residual and the U term vanish without a
 // select.  The kernel accumulates sum mu; sum_n y_n eta_n = <X^T y, b> + sum_n y_n o_n, and with
 // sum_n lgamma(y_n + 1) that is the X^T y table plus ONE float64 scalar of the pack.  D <= 64 runs
-// the 4 x 1 class with DTS = 1 or 2 (instantiated for this policy only).  A chain whose eta passes
+// the 4 x 1 class with DTS = 1 or 2 (instantiated for this policy and for the horseshoe prior below
+// only).  A chain whose eta passes
 // float32's exp range gets mu = +inf in its own B-operand column: U = +inf (the float64 parts are
 // finite), and no other chain changes by a bit.
+//
+// The prior is a second compile-time policy PR: where the coefficient fragments at the top of
+// k_logreg_wide come from, and which finalize follows.  pr_normal is the prior above (arena row d is
+// the coefficient).  pr_horseshoe is sparse regression, for either likelihood and 1 <= D <= 1024:
+//
+//   lambdas ~ HalfCauchy(1)^D, tau ~ HalfCauchy(1), unscaled_betas ~ N(0, 1)^D,
+//   betas = tau lambdas unscaled_betas,  obs ~ LK(X @ betas)
+//
+// on the 2 D + 1 unconstrained arena rows ul[d] = log lambdas[d] (row d), ut = log tau (row D) and
+// z[d] (row D + 1 + d).  With s[d] = exp(ut + ul[d]), beta[d] = s[d] z[d] (hs_coef, float32) and L the
+// likelihood part above, G = dL/dbeta = X^T residual:
+//
+//   U      = L(beta) + sum_d [log(2 cosh ul[d]) + log(pi / 2)] + log(2 cosh ut) + log(pi / 2)
+//            + sum_d [z[d]^2 / 2 + log(2 pi) / 2]
+//   dU/dz[d] = s[d] G[d] + z[d],  dU/dul[d] = beta[d] G[d] + tanh(ul[d]),
+//   dU/dut   = sum_d beta[d] G[d] + tanh(ut)
+//
+// The tile kernel is the same but for the gather (three arena rows and hs_coef before the split), so
+// the slabs hold G.  dU/dut sums over coordinates, which no workgroup of the plain finalize does, so
+// the horseshoe has a finalize of its own in two launches:
+//   k_horseshoe_finalize  one workgroup per (64 positions, block of HS_BLOCK coordinates), wave w the
+//     coordinates w HS_BLOCK / 4 .. of the block, one after the other: G[d] from the S slabs in the
+//     plain finalize's order (four quarters, then ((q0 + q1) + q2) + q3), beta[d] by hs_coef again,
+//     the z and ul gradient rows, and in float64 the wave's running beta G and its part of U
+//     (log 2 cosh ul + z^2 / 2 - xty beta: the linear part of U is in beta); the four waves' sums are
+//     added in wave order and go to the block's two workspace rows;
+//   k_horseshoe_tau       one workgroup per 64 positions: wave w adds its quarter of the pepart slabs
+//     and the blocks [w NB / 4, (w + 1) NB / 4) in block order, the four are added in wave order, then
+//     tau's own terms and the constants: the ut gradient row and U.
+// NB = ceil(D / HS_BLOCK): every order above is a function of D and S alone.  No atomics.  A chain whose
+// ut + ul[d] passes float32's exp range has beta = +-inf in its own B-operand column and in its own
+// float64 sums: U is not finite, and no other chain changes by a bit.
 #include <math.h>
 #include <stdlib.h>
 
@@ -346,6 +379,39 @@ struct lk_poisson {
   }
 };
 
+// Horseshoe scale and coefficient of one coordinate, s = exp(ut + ul) and beta = s z in float32: the
+// gather of k_logreg_wide and k_horseshoe_finalize both go through here, and the pinned sum keeps
+// either from contracting it into the exponential's first product, so both see the same bits.
+__device__ __forceinline__ void hs_coef(float ul, float ut, float z, float& s, float& beta) {
+  float u = ut + ul;
+  lw_pin(u);
+  s = expf(u);
+  beta = s * z;
+}
+
+// The prior policies: whether every width from 1 is served (the 4 x 1 class with DTS = 1 and 2 for
+// any likelihood), and what the kernel's load of arena row d (rows of ldc) of chain c is.  pr_normal:
+// the coefficient itself.  pr_horseshoe: ul[d], which `coef` turns into beta[d].
+struct pr_normal {
+  static constexpr bool ALL_D = false, HORSESHOE = false;
+};
+struct pr_horseshoe {
+  static constexpr bool ALL_D = true, HORSESHOE = true;
+  static __device__ __forceinline__ float coef(float v, const nmx_eval_batch& ev, int d, int D, int ldc, int c) {
+    float s, beta;
+    hs_coef(v, ev.z[(size_t)D * ldc + c], ev.z[(size_t)(D + 1 + d) * ldc + c], s, beta);
+    return beta;
+  }
+};
+template <class LK, class PR>
+constexpr int lw_min_d() {
+  return PR::ALL_D ? 1 : LK::MIN_D;
+}
+template <class LK, class PR>
+constexpr const char* lw_name() {
+  return PR::HORSESHOE ? "horseshoe" : LK::NAME;
+}
+
 template <int CT, int DS, int DTS, int R>
 struct lw_cfg {
   static constexpr int WAVES = CT * DS, NCH = 2 * DTS, KBS = 2 * DTS, DW = 32 * DTS;
@@ -362,7 +428,7 @@ struct lw_cfg {
   static_assert(LDS_BYTES <= 160 * 1024, "the CU's LDS");
 };
 
-template <class LK, int CT, int DS, int DTS, int R>
+template <class LK, class PR, int CT, int DS, int DTS, int R>
 __global__ __launch_bounds__(64 * CT * DS) void k_logreg_wide(const char* __restrict__ Xq, int64_t ntiles, int D,
                                                               int S, int Gt, nmx_eval_batch ev,
                                                               float* __restrict__ gpart,
@@ -394,8 +460,8 @@ __global__ __launch_bounds__(64 * CT * DS) void k_logreg_wide(const char* __rest
       (void*)(Xq + (size_t)t0 * C::TILE_BYTES), 0, (int)((size_t)nt * C::TILE_BYTES), 0x00020000);
 
   // coefficient fragments of the slice (B operand: lane (col, h) holds Z[d0 + 16 kb + 8 h + j] of
-  // its chain), gathered from the arena once and split; features >= D and lanes without a chain
-  // hold zero
+  // its chain), gathered from the arena once, through the prior policy, and split; features >= D
+  // and lanes without a chain hold zero
   // (clamped loads, masked after: a load under `ok` compiles to a branch and a wait per element)
   const int d0 = sl * C::DW;
   const int cz = c >= 0 ? c : 0;
@@ -408,6 +474,13 @@ __global__ __launch_bounds__(64 * CT * DS) void k_logreg_wide(const char* __rest
       const int d = d0 + 16 * kb + 8 * h + j;
       NMX_DCHECK(d >= 0 && cz < ldc);
       v[j] = ev.z[(size_t)(d < D ? d : D - 1) * ldc + cz];
+    }
+    if constexpr (PR::HORSESHOE) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int d = d0 + 16 * kb + 8 * h + j;
+        v[j] = PR::coef(v[j], ev, d < D ? d : D - 1, D, ldc, cz);
+      }
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = (c >= 0 && d0 + 16 * kb + 8 * h + j < D) ? v[j] : 0.0f;
@@ -656,6 +729,112 @@ __global__ __launch_bounds__(64 * FIN_WAVES) void k_logreg_wide_finalize(const f
   }
 }
 
+// The horseshoe's finalize (see the header): k_horseshoe_finalize per (64 positions, block of
+// HS_BLOCK coordinates), then k_horseshoe_tau per 64 positions.  upart / tpart are [NB][ldc] float64
+// rows of the workspace, indexed by position like pepart.
+constexpr int HS_BLOCK = 8, HS_PER_WAVE = HS_BLOCK / FIN_WAVES;
+constexpr double HS_LOG_HALF_PI = 0.4515827052894548, HS_HALF_LOG_2PI = 0.9189385332046727;
+inline int hs_num_blocks(int D) { return (D + HS_BLOCK - 1) / HS_BLOCK; }
+
+// log(2 cosh u): -log of HalfCauchy(1)'s density at exp(u) times the Jacobian exp(u), less log(pi / 2)
+__device__ __forceinline__ double hs_log2cosh(double u) {
+  const double a = fabs(u);
+  return a + log1p(exp(-2.0 * a));
+}
+
+__global__ __launch_bounds__(64 * FIN_WAVES) void k_horseshoe_finalize(const float* __restrict__ gpart, int S, int D,
+                                                                       nmx_eval_batch ev,
+                                                                       const double* __restrict__ xty,
+                                                                       double* __restrict__ upart,
+                                                                       double* __restrict__ tpart) {
+  __shared__ double part[2][FIN_WAVES][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int pos = blockIdx.x * 64 + lane;
+  const int blk = blockIdx.y;
+  const int ldc = ev.ldc;
+  const int c = pos < ldc ? nmx_eval_chain(ev, pos) : -1;
+  const int Q = S / FIN_WAVES;  // S is a multiple of 8 (lw_num_splits)
+  double u = 0.0, t = 0.0;
+  if (c >= 0) {
+    const float ut = ev.z[(size_t)D * ldc + c];
+    for (int k = 0; k < HS_PER_WAVE; ++k) {
+      const int j = blk * HS_BLOCK + w * HS_PER_WAVE + k;
+      if (j >= D) break;
+      // the plain finalize's order: the four quarters of the slabs, each in slab order, then q0..q3
+      float f[FIN_WAVES] = {0.0f, 0.0f, 0.0f, 0.0f};
+      for (int i = 0; i < Q; ++i)
+#pragma unroll
+        for (int q = 0; q < FIN_WAVES; ++q) {
+          NMX_DCHECK(q * Q + i < S && j < D && pos < ldc);
+          f[q] += gpart[((size_t)(q * Q + i) * D + j) * ldc + pos];
+        }
+      float G = 0.0f;
+#pragma unroll
+      for (int q = 0; q < FIN_WAVES; ++q) G += f[q];
+      const size_t iul = (size_t)j * ldc + c, iz = (size_t)(D + 1 + j) * ldc + c;
+      const float ul = ev.z[iul], z = ev.z[iz];
+      float s, beta;
+      hs_coef(ul, ut, z, s, beta);
+      ev.grad[iz] = s * G + z;
+      ev.grad[iul] = beta * G + tanhf(ul);
+      t += (double)beta * (double)G;
+      u += hs_log2cosh((double)ul) + 0.5 * (double)z * (double)z - xty[j] * (double)beta;
+    }
+  }
+  part[0][w][lane] = u;
+  part[1][w][lane] = t;
+  __syncthreads();
+  if (w != 0 || c < 0) return;
+  u = 0.0, t = 0.0;
+#pragma unroll
+  for (int i = 0; i < FIN_WAVES; ++i) {
+    u += part[0][i][lane];
+    t += part[1][i][lane];
+  }
+  upart[(size_t)blk * ldc + pos] = u;
+  tpart[(size_t)blk * ldc + pos] = t;
+}
+
+template <class LK>
+__global__ __launch_bounds__(64 * FIN_WAVES) void k_horseshoe_tau(const double* __restrict__ pepart,
+                                                                  const double* __restrict__ upart,
+                                                                  const double* __restrict__ tpart, int S, int D,
+                                                                  int NB, nmx_eval_batch ev,
+                                                                  const double* __restrict__ xty) {
+  __shared__ double part[2][FIN_WAVES][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int pos = blockIdx.x * 64 + lane;
+  const int ldc = ev.ldc;
+  const int c = pos < ldc ? nmx_eval_chain(ev, pos) : -1;
+  double u = 0.0, t = 0.0;
+  if (c >= 0) {
+    for (int sp = w * S / FIN_WAVES; sp < (w + 1) * S / FIN_WAVES; ++sp) u += pepart[(size_t)sp * ldc + pos];
+    double ub = 0.0;
+    for (int b = w * NB / FIN_WAVES; b < (w + 1) * NB / FIN_WAVES; ++b) {
+      NMX_DCHECK(b < NB);
+      ub += upart[(size_t)b * ldc + pos];
+      t += tpart[(size_t)b * ldc + pos];
+    }
+    u += ub;
+  }
+  part[0][w][lane] = u;
+  part[1][w][lane] = t;
+  __syncthreads();
+  if (w != 0 || c < 0) return;
+  u = 0.0, t = 0.0;
+#pragma unroll
+  for (int i = 0; i < FIN_WAVES; ++i) {
+    u += part[0][i][lane];
+    t += part[1][i][lane];
+  }
+  const size_t iut = (size_t)D * ldc + c;
+  const double ut = ev.z[iut];
+  ev.grad[iut] = (float)(t + tanh(ut));
+  u += hs_log2cosh(ut) + (D + 1) * HS_LOG_HALF_PI + D * HS_HALF_LOG_2PI;
+  if constexpr (LK::HEAD_BYTES > 0) u += xty[LW_MAX_D];
+  ev.pe[c] = (float)u;
+}
+
 bool lw_shape_ok(int64_t n_rows, int dim, int min_d) { return n_rows > 0 && dim >= min_d && dim <= LW_MAX_D; }
 
 int lw_check_shape(const char* name, const char* fn, int64_t n_rows, int dim, int min_d) {
@@ -681,30 +860,30 @@ struct lw_args {
   float* gpart;
   double* pepart;
 };
-template <class LK, int CT, int DS, int DTS, int R>
+template <class LK, class PR, int CT, int DS, int DTS, int R>
 int lw_launch(const lw_args& a) {
   using C = lw_cfg<CT, DS, DTS, R>;
-  if (int st = nmx_lds_limit((const void*)k_logreg_wide<LK, CT, DS, DTS, R>, C::LDS_BYTES, a.s, "k_logreg_wide"))
+  if (int st = nmx_lds_limit((const void*)k_logreg_wide<LK, PR, CT, DS, DTS, R>, C::LDS_BYTES, a.s, "k_logreg_wide"))
     return st;
-  hipLaunchKernelGGL((k_logreg_wide<LK, CT, DS, DTS, R>), a.grid, dim3(64 * C::WAVES), C::LDS_BYTES, a.s, a.Xq, a.nt, a.D,
-                     a.S, a.Gt, a.ev, a.gpart, a.pepart);
+  hipLaunchKernelGGL((k_logreg_wide<LK, PR, CT, DS, DTS, R>), a.grid, dim3(64 * C::WAVES), C::LDS_BYTES, a.s, a.Xq, a.nt,
+                     a.D, a.S, a.Gt, a.ev, a.gpart, a.pepart);
   return NMX_OK;
 }
-// DTS = 3 or 4 from 65 features on; 1 or 2 below, in the 4 x 1 class of a policy that serves them
-template <class LK, int CT, int DS, int R>
+// DTS = 3 or 4 from 65 features on; 1 or 2 below, in the 4 x 1 class of policies that serve them
+template <class LK, class PR, int CT, int DS, int R>
 int lw_launch_dts(int DTS, const lw_args& a) {
-  if constexpr (LK::MIN_D <= 64 && DS == 1) {
-    if (DTS == 1) return lw_launch<LK, CT, DS, 1, R>(a);
-    if (DTS == 2) return lw_launch<LK, CT, DS, 2, R>(a);
+  if constexpr (lw_min_d<LK, PR>() <= 64 && DS == 1) {
+    if (DTS == 1) return lw_launch<LK, PR, CT, DS, 1, R>(a);
+    if (DTS == 2) return lw_launch<LK, PR, CT, DS, 2, R>(a);
   }
-  if (DTS == 3) return lw_launch<LK, CT, DS, 3, R>(a);
-  return lw_launch<LK, CT, DS, 4, R>(a);
+  if (DTS == 3) return lw_launch<LK, PR, CT, DS, 3, R>(a);
+  return lw_launch<LK, PR, CT, DS, 4, R>(a);
 }
 
-// The four entry points of a policy.
-template <class LK>
+// The four entry points of a pair of policies (the pack is the likelihood's alone).
+template <class LK, class PR = pr_normal>
 size_t lw_packed_bytes(int64_t n_rows, int dim) {
-  if (!lw_shape_ok(n_rows, dim, LK::MIN_D)) return 0;
+  if (!lw_shape_ok(n_rows, dim, lw_min_d<LK, PR>())) return 0;
   return LW_XTY_BYTES + LK::HEAD_BYTES + (size_t)lw_ntiles(n_rows) * lw_tile_bytes(dim);
 }
 
@@ -720,24 +899,26 @@ int lw_pack(const float* X, const float* y, const float* off, int64_t n_rows, in
   return nmx_check_launch("k_logreg_wide_pack");
 }
 
-template <class LK>
+// workspace: the gradient slabs | the U slabs | (horseshoe) the blocks' U rows | their beta G rows
+template <class LK, class PR = pr_normal>
 size_t lw_workspace_bytes(int64_t n_rows, int dim, int num_chains) {
-  if (!lw_shape_ok(n_rows, dim, LK::MIN_D) || num_chains <= 0) return 0;
+  if (!lw_shape_ok(n_rows, dim, lw_min_d<LK, PR>()) || num_chains <= 0) return 0;
   const size_t ldc = (size_t)(num_chains + 63) / 64 * 64;
   const size_t S = lw_num_splits(n_rows, dim);
   const size_t g = S * dim * ldc * sizeof(float);
-  const size_t p = S * ldc * sizeof(double);
+  const size_t p = (S + (PR::HORSESHOE ? 2 * hs_num_blocks(dim) : 0)) * ldc * sizeof(double);
   return (g + 255) / 256 * 256 + p;
 }
 
-template <class LK>
+template <class LK, class PR = pr_normal>
 int lw_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch* ev, void* workspace, void* stream) {
-  if (int st = lw_check_shape(LK::NAME, "pe_grad", n_rows, dim, LK::MIN_D)) return st;
+  constexpr const char* NAME = lw_name<LK, PR>();
+  if (int st = lw_check_shape(NAME, "pe_grad", n_rows, dim, lw_min_d<LK, PR>())) return st;
   if (!ev || !ev->z || !ev->grad || !ev->pe)
-    return nmx_fail(NMX_ERR_INVALID, "%s_pe_grad: eval batch has NULL pointers", LK::NAME);
+    return nmx_fail(NMX_ERR_INVALID, "%s_pe_grad: eval batch has NULL pointers", NAME);
   if (ev->num_chains <= 0 || ev->ldc < ev->num_chains || ev->ldc % 64)
-    return nmx_fail(NMX_ERR_INVALID, "%s_pe_grad: bad num_chains/ldc (%d/%d)", LK::NAME, ev->num_chains, ev->ldc);
-  if (!packed || !workspace) return nmx_fail(NMX_ERR_INVALID, "%s_pe_grad: NULL packed/workspace", LK::NAME);
+    return nmx_fail(NMX_ERR_INVALID, "%s_pe_grad: bad num_chains/ldc (%d/%d)", NAME, ev->num_chains, ev->ldc);
+  if (!packed || !workspace) return nmx_fail(NMX_ERR_INVALID, "%s_pe_grad: NULL packed/workspace", NAME);
   hipStream_t s = (hipStream_t)stream;
   const int S = lw_num_splits(n_rows, dim);
   float* gpart = (float*)workspace;
@@ -748,15 +929,44 @@ int lw_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch
   const lw_args a = {dim3((unsigned)Gt * S), s,  (const char*)packed + LW_XTY_BYTES + LK::HEAD_BYTES,
                      lw_ntiles(n_rows),      dim, S, Gt, *ev, gpart, pepart};
   int st;
-  if (c.DS == 1) st = lw_launch_dts<LK, 4, 1, 3>(c.DTS, a);
-  else if (c.DS == 2) st = lw_launch_dts<LK, 4, 2, 3>(c.DTS, a);
-  else if (c.DS == 4) st = lw_launch_dts<LK, 2, 4, 3>(c.DTS, a);
-  else st = lw_launch_dts<LK, 1, 8, 2>(c.DTS, a);
+  if (c.DS == 1) st = lw_launch_dts<LK, PR, 4, 1, 3>(c.DTS, a);
+  else if (c.DS == 2) st = lw_launch_dts<LK, PR, 4, 2, 3>(c.DTS, a);
+  else if (c.DS == 4) st = lw_launch_dts<LK, PR, 2, 4, 3>(c.DTS, a);
+  else st = lw_launch_dts<LK, PR, 1, 8, 2>(c.DTS, a);
   if (st) return st;
   if (int e = nmx_check_launch("k_logreg_wide")) return e;
-  hipLaunchKernelGGL(k_logreg_wide_finalize<LK>, dim3((nb + 63) / 64, dim + 1), dim3(64 * FIN_WAVES), 0, s, gpart,
-                     pepart, S, dim, *ev, (const double*)packed);
-  return nmx_check_launch("k_logreg_wide_finalize");
+  if constexpr (PR::HORSESHOE) {
+    const int NB = hs_num_blocks(dim);
+    double* upart = pepart + (size_t)S * ev->ldc;
+    double* tpart = upart + (size_t)NB * ev->ldc;
+    hipLaunchKernelGGL(k_horseshoe_finalize, dim3((nb + 63) / 64, NB), dim3(64 * FIN_WAVES), 0, s, gpart, S, dim, *ev,
+                       (const double*)packed, upart, tpart);
+    if (int e = nmx_check_launch("k_horseshoe_finalize")) return e;
+    hipLaunchKernelGGL(k_horseshoe_tau<LK>, dim3((nb + 63) / 64), dim3(64 * FIN_WAVES), 0, s, pepart, upart, tpart, S,
+                       dim, NB, *ev, (const double*)packed);
+    return nmx_check_launch("k_horseshoe_tau");
+  } else {
+    hipLaunchKernelGGL(k_logreg_wide_finalize<LK>, dim3((nb + 63) / 64, dim + 1), dim3(64 * FIN_WAVES), 0, s, gpart,
+                       pepart, S, dim, *ev, (const double*)packed);
+    return nmx_check_launch("k_logreg_wide_finalize");
+  }
+}
+
+// Synchronises the stream once, to refuse a bad count before anything is packed.
+int lw_poisson_pack(const char* name, const float* X, const float* y, const float* offset, int64_t n_rows, int dim,
+                    void* packed, hipStream_t s) {
+  double* head = (double*)((char*)packed + LW_XTY_BYTES);
+  unsigned long long* bad = (unsigned long long*)(head + 1);
+  hipLaunchKernelGGL(k_poisson_bad_reset, dim3(1), dim3(1), 0, s, bad);
+  hipLaunchKernelGGL(k_poisson_const, dim3(1), dim3(CS_THREADS), 0, s, y, offset, n_rows, head, bad);
+  if (int st = nmx_check_launch("k_poisson_const")) return st;
+  unsigned long long first = 0;
+  if (hipMemcpyAsync(&first, bad, sizeof(first), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return nmx_fail(NMX_ERR_HIP, "%s_pack: reading the count check back failed", name);
+  if (first != ~0ull)
+    return nmx_fail(NMX_ERR_INVALID, "%s_pack: the count of row %llu is not a whole number in [0, 2^24)", name, first);
+  return lw_pack<lk_poisson>(X, y, offset, n_rows, dim, packed, s);
 }
 
 }  // namespace
@@ -788,19 +998,7 @@ extern "C" int nmx_poisson_pack(const float* X, const float* y, const float* off
                                 void* packed, void* stream) {
   if (int st = lw_check_shape("poisson", "pack", n_rows, dim, lk_poisson::MIN_D)) return st;
   if (!X || !y || !packed) return nmx_fail(NMX_ERR_INVALID, "poisson_pack: NULL pointer");
-  hipStream_t s = (hipStream_t)stream;
-  double* head = (double*)((char*)packed + LW_XTY_BYTES);
-  unsigned long long* bad = (unsigned long long*)(head + 1);
-  hipLaunchKernelGGL(k_poisson_bad_reset, dim3(1), dim3(1), 0, s, bad);
-  hipLaunchKernelGGL(k_poisson_const, dim3(1), dim3(CS_THREADS), 0, s, y, offset, n_rows, head, bad);
-  if (int st = nmx_check_launch("k_poisson_const")) return st;
-  unsigned long long first = 0;
-  if (hipMemcpyAsync(&first, bad, sizeof(first), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
-    return nmx_fail(NMX_ERR_HIP, "poisson_pack: reading the count check back failed");
-  if (first != ~0ull)
-    return nmx_fail(NMX_ERR_INVALID, "poisson_pack: the count of row %llu is not a whole number in [0, 2^24)", first);
-  return lw_pack<lk_poisson>(X, y, offset, n_rows, dim, packed, s);
+  return lw_poisson_pack("poisson", X, y, offset, n_rows, dim, packed, (hipStream_t)stream);
 }
 
 extern "C" size_t nmx_poisson_workspace_bytes(int64_t n_rows, int dim, int num_chains) {
@@ -810,4 +1008,40 @@ extern "C" size_t nmx_poisson_workspace_bytes(int64_t n_rows, int dim, int num_c
 extern "C" int nmx_poisson_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch* ev,
                                    void* workspace, void* stream) {
   return lw_pe_grad<lk_poisson>(packed, n_rows, dim, ev, workspace, stream);
+}
+
+// Horseshoe-prior regression: `likelihood` is 0 (Bernoulli logits) or 1 (Poisson, log link); `dim`
+// is the number of features D, the arena has 2 D + 1 rows.
+namespace {
+int hs_check_likelihood(const char* fn, int likelihood) {
+  if (likelihood == 0 || likelihood == 1) return NMX_OK;
+  return nmx_fail(NMX_ERR_INVALID, "horseshoe_%s: likelihood is 0 (Bernoulli) or 1 (Poisson) (got %d)", fn, likelihood);
+}
+}  // namespace
+
+extern "C" size_t nmx_horseshoe_packed_bytes(int likelihood, int64_t n_rows, int dim) {
+  if (likelihood == 0) return lw_packed_bytes<lk_bernoulli, pr_horseshoe>(n_rows, dim);
+  return likelihood == 1 ? lw_packed_bytes<lk_poisson, pr_horseshoe>(n_rows, dim) : 0;
+}
+
+extern "C" int nmx_horseshoe_pack(int likelihood, const float* X, const float* y, const float* offset, int64_t n_rows,
+                                  int dim, void* packed, void* stream) {
+  if (int st = hs_check_likelihood("pack", likelihood)) return st;
+  if (int st = lw_check_shape("horseshoe", "pack", n_rows, dim, 1)) return st;
+  if (!X || !y || !packed) return nmx_fail(NMX_ERR_INVALID, "horseshoe_pack: NULL pointer");
+  if (likelihood == 1) return lw_poisson_pack("horseshoe", X, y, offset, n_rows, dim, packed, (hipStream_t)stream);
+  if (offset) return nmx_fail(NMX_ERR_INVALID, "horseshoe_pack: the Bernoulli likelihood takes no offset");
+  return lw_pack<lk_bernoulli>(X, y, nullptr, n_rows, dim, packed, (hipStream_t)stream);
+}
+
+extern "C" size_t nmx_horseshoe_workspace_bytes(int likelihood, int64_t n_rows, int dim, int num_chains) {
+  if (likelihood == 0) return lw_workspace_bytes<lk_bernoulli, pr_horseshoe>(n_rows, dim, num_chains);
+  return likelihood == 1 ? lw_workspace_bytes<lk_poisson, pr_horseshoe>(n_rows, dim, num_chains) : 0;
+}
+
+extern "C" int nmx_horseshoe_pe_grad(int likelihood, const void* packed, int64_t n_rows, int dim,
+                                     const nmx_eval_batch* ev, void* workspace, void* stream) {
+  if (int st = hs_check_likelihood("pe_grad", likelihood)) return st;
+  if (likelihood == 0) return lw_pe_grad<lk_bernoulli, pr_horseshoe>(packed, n_rows, dim, ev, workspace, stream);
+  return lw_pe_grad<lk_poisson, pr_horseshoe>(packed, n_rows, dim, ev, workspace, stream);
 }

@@ -9,7 +9,7 @@ differentiates it with JAX.  Here the trace records each site's distribution, pa
 observed data; a matcher per supported structure checks the priors' constants and the
 likelihood's expression and returns the bound fused potential, with the model's own site
 names.  Supported structures: the reference's examples on the hot path (covtype logistic
-regression, its multi-class form, softmax regression, and Poisson regression; eight schools,
+regression, its multi-class form, softmax regression, Poisson regression, and horseshoe regression; eight schools,
 funnel and its LocScaleReparam(0) form, stochastic volatility, the BNN) and the test targets (diagonal normal, multivariate normal).  For anything else
 potential_from_model raises NotImplementedError naming the traced sites; NUTS / HMC then hand
 the model to the program compiler (numpyro_amd/program.py compile_model), which lowers the
@@ -206,6 +206,70 @@ def _match_poisson(trace):
     return _renamed(P.PoissonRegression(X, o.obs, offset), {"coefs": w.name})
 
 
+def _product_latents(x):
+    """The latent names of a product of latent sites in any association, or None."""
+    if _latent(x):
+        return [x.args[0]]
+    if isinstance(x, Sym) and x.op == "mul":
+        a, b = (_product_latents(v) for v in x.args)
+        return None if a is None or b is None else a + b
+    return None
+
+
+def _match_horseshoe(trace):
+    """examples/horseshoe_regression.py:62-78: lambdas ~ HalfCauchy(1)^D, tau ~ HalfCauchy(1) of shape
+    (1,) or (), unscaled_betas ~ Normal(0, 1)^D, and Y ~ Bernoulli(logits=X @ p) or
+    Poisson(exp(X @ p [+ offset])), p the product of the three in any order, written directly or
+    through numpyro.deterministic (which keeps its name).  Nothing else: no other scale, latent or
+    term, D <= 1024, labels 0 or 1 / whole counts."""
+    lat, obs = _split(trace)
+    if len(lat) != 3 or len(obs) != 1 or trace.reparam:
+        return None
+    half = [s for s in lat if _is(s.fn, dist.HalfCauchy) and _const(_base(s.fn).scale, 1.0)]
+    z = [s for s in lat if _std_normal(s) and len(s.shape) == 1]
+    if len(half) != 2 or len(z) != 1:
+        return None
+    z, D = z[0], z[0].shape[0]
+    lam = [s for s in half if s.shape == (D,)][:1]
+    tau = [s for s in half if s not in lam and s.shape in ((1,), ())]
+    if not lam or not tau or not 1 <= D <= P.HorseshoeRegression.MAX_FEATURES:
+        return None
+    lam, tau, o = lam[0], tau[0], obs[0]
+    offset = None
+    if _is(o.fn, dist.BernoulliLogits):
+        likelihood, eta = "bernoulli", _base(o.fn).logits
+    elif _is(o.fn, dist.Poisson):
+        likelihood, rate = "poisson", _base(o.fn).rate
+        if not (isinstance(rate, Sym) and rate.op == "exp"):
+            return None
+        eta = rate.args[0]
+        if isinstance(eta, Sym) and eta.op == "add":
+            a, b = eta.args
+            eta, offset = (a, b) if isinstance(a, Sym) else (b, a)
+    else:
+        return None
+    if not (isinstance(eta, Sym) and eta.op == "matmul" and _const(eta.args[0])):
+        return None
+    X, p = eta.args
+    if sorted(_product_latents(p) or []) != sorted(s.name for s in lat):
+        return None
+    N = shape_of(X)[0]
+    if len(shape_of(X)) != 2 or shape_of(X)[1] != D or tuple(shape_of(o.obs)) != (N,):
+        return None
+    if offset is not None and not (_const(offset) and tuple(shape_of(offset)) == (N,)):
+        return None
+    if not (P.poisson_counts_ok(o.obs) if likelihood == "poisson" else P.bernoulli_labels_ok(o.obs)):
+        return None
+    pot = P.HorseshoeRegression(X, o.obs, likelihood, offset)
+    if tau.shape == ():
+        pot.sites[1] = ("tau", (), P.POSITIVE)
+    det = [name for name, value in trace.deterministics.items() if value is p]
+    if not det:  # the product is no site of this model
+        pot.deterministic = lambda sites: {}
+    return _renamed(pot, {"lambdas": lam.name, "tau": tau.name, "unscaled_betas": z.name,
+                          "betas": (det or ["betas"])[0]})
+
+
 def softmax_structure(trace):
     """(coefs site, label site, X) of coefs ~ Normal(0, 1) [D, K], obs ~ Categorical(logits=X @ coefs)
     with X [N, D] and D, K inside the fused kernels' limits, or None.  The label site may be
@@ -381,7 +445,7 @@ def _match_normal(trace):
     return None
 
 
-MATCHERS = (_match_logistic, _match_poisson, _match_softmax, _match_eight_schools, _match_funnel, _match_sv, _match_bnn,
+MATCHERS = (_match_logistic, _match_poisson, _match_horseshoe, _match_softmax, _match_eight_schools, _match_funnel, _match_sv, _match_bnn,
             _match_normal)
 
 
@@ -396,7 +460,7 @@ def potential_from_model(model, args=(), kwargs=None):
             return _with_traced_deterministics(pot, trace)
     raise NotImplementedError(
         "no fused kernel for this model structure (sites: " + ", ".join(map(repr, trace.sites.values())) +
-        "); supported: the reference's covtype logistic regression, softmax regression, Poisson regression, eight schools, funnel (+ LocScaleReparam), "
+        "); supported: the reference's covtype logistic regression, softmax regression, Poisson regression, horseshoe regression (Bernoulli / Poisson), eight schools, funnel (+ LocScaleReparam), "
         "stochastic volatility and BNN examples, and diagonal / multivariate normal targets")
 
 

@@ -248,6 +248,10 @@ SIGNATURES: dict[str, tuple] = {
     "nmx_poisson_pack": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     "nmx_poisson_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
     "nmx_poisson_pe_grad": (c_int, [c_vp, c_i64, c_int, _evp, c_vp, c_vp]),
+    "nmx_horseshoe_packed_bytes": (c_size, [c_int, c_i64, c_int]),
+    "nmx_horseshoe_pack": (c_int, [c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
+    "nmx_horseshoe_workspace_bytes": (c_size, [c_int, c_i64, c_int, c_int]),
+    "nmx_horseshoe_pe_grad": (c_int, [c_int, c_vp, c_i64, c_int, _evp, c_vp, c_vp]),
     "nmx_softmax_packed_bytes": (c_size, [c_i64, c_int, c_int]),
     "nmx_softmax_pack": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp]),
     "nmx_softmax_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int]),

@@ -248,6 +248,12 @@ def poisson_counts_ok(counts):
     return y.dtype.kind in "iuf" and bool(np.all((y >= 0) & (y < 2 ** 24) & (y == np.floor(y))))
 
 
+def bernoulli_labels_ok(labels):
+    """Labels that are all 0 or 1."""
+    y = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+    return y.dtype.kind in "biuf" and bool(np.all((y == 0) | (y == 1)))
+
+
 class PoissonRegression(Potential):
     """Count regression: coefs ~ N(0, 1)^D, obs ~ Poisson(exp(X @ coefs + offset)), 1 to 1024
     features, on the D-blocked kernel of csrc/potential_logreg_wide.hip with the Poisson likelihood
@@ -299,6 +305,77 @@ class PoissonRegression(Potential):
     def flops_per_eval(self, num_chains):
         """Algorithmic FLOPs of one evaluation (two GEMMs): 4 N D C."""
         return 4.0 * self.N * self.dim * num_chains
+
+
+class HorseshoeRegression(Potential):
+    """examples/horseshoe_regression.py:62-78, sparse regression with a horseshoe prior:
+    lambdas ~ HalfCauchy(1)^D, tau ~ HalfCauchy(1) [1], unscaled_betas ~ N(0, 1)^D,
+    betas = tau * lambdas * unscaled_betas (a deterministic site), and obs ~ Bernoulli(logits=X @ betas)
+    or, with ``likelihood="poisson"``, Poisson(exp(X @ betas + offset)).  1 to 1024 features on the
+    D-blocked kernel of csrc/potential_logreg_wide.hip with the horseshoe prior policy (the
+    ``nmx_horseshoe_*`` entry points); 2 D + 1 coordinates."""
+
+    MAX_FEATURES = 1024
+    LIKELIHOODS = {"bernoulli": 0, "poisson": 1}  # the entry points' likelihood code
+
+    def __init__(self, data, obs, likelihood="bernoulli", offset=None):
+        if likelihood not in self.LIKELIHOODS:
+            raise ValueError(f"horseshoe regression has the likelihoods {sorted(self.LIKELIHOODS)} (got {likelihood!r})")
+        self.X_in, self.y_in, self.o_in, self.likelihood = data, obs, offset, likelihood
+        shape, yshape = tuple(data.shape), tuple(getattr(obs, "shape", None) or np.shape(obs))
+        if len(shape) != 2 or yshape != shape[:1]:
+            raise ValueError(f"horseshoe regression needs data [N, D] and observations [N] (got {shape}, {yshape})")
+        if offset is not None and likelihood != "poisson":
+            raise ValueError("horseshoe regression takes an offset with the Poisson likelihood only")
+        if offset is not None and tuple(getattr(offset, "shape", None) or np.shape(offset)) != yshape:
+            raise ValueError(f"horseshoe regression needs an offset of shape {list(yshape)}")
+        self.N, self.D = int(shape[0]), int(shape[1])
+        if not 1 <= self.D <= self.MAX_FEATURES:
+            raise ValueError(f"the fused horseshoe-regression kernel supports 1 to {self.MAX_FEATURES} features "
+                             f"(got {self.D})")
+        if likelihood == "poisson" and not poisson_counts_ok(obs):
+            raise ValueError("horseshoe regression needs counts that are whole numbers in [0, 2^24)")
+        if likelihood == "bernoulli" and not bernoulli_labels_ok(obs):
+            raise ValueError("horseshoe regression needs labels that are 0 or 1")
+        self.dim = 2 * self.D + 1
+        self.sites = [("lambdas", (self.D,), POSITIVE), ("tau", (1,), POSITIVE), ("unscaled_betas", (self.D,), REAL)]
+        self.packed = None
+
+    slots = 4  # workspaces, as LogisticRegression
+
+    def _bind(self, C, ldc, device):
+        code = self.LIKELIHOODS[self.likelihood]
+        if self.packed is None or self.packed.device != device:
+            X, y = _dev(self.X_in, device), _dev(self.y_in, device)
+            o = None if self.o_in is None else _dev(self.o_in, device)
+            nb = lib().nmx_horseshoe_packed_bytes(code, self.N, self.D)
+            self.packed = torch.empty(nb // 4, dtype=torch.float32, device=device)
+            with torch.cuda.device(device):
+                check(lib().nmx_horseshoe_pack(code, ptr(X), ptr(y), ptr(o), self.N, self.D, ptr(self.packed),
+                                               native.stream_ptr()), "nmx_horseshoe_pack")
+            del X, y, o
+        wb = lib().nmx_horseshoe_workspace_bytes(code, self.N, self.D, ldc)  # the slabs' rows are ldc wide
+        self.workspace = torch.empty(wb, dtype=torch.uint8, device=device)
+        self._more_ws = []  # slots 1.. (allocated on first use)
+
+    def evaluate(self, ev, stream, slot=0):
+        ws = self.workspace
+        if slot:
+            while len(self._more_ws) < slot:
+                self._more_ws.append(torch.empty_like(self.workspace))
+            ws = self._more_ws[slot - 1]
+        check(lib().nmx_horseshoe_pe_grad(self.LIKELIHOODS[self.likelihood], ptr(self.packed), self.N, self.D,
+                                          ctypes.byref(ev), ptr(ws), stream), "nmx_horseshoe_pe_grad")
+
+    def deterministic(self, sites):
+        tau = sites["tau"]
+        if tau.dim() < sites["lambdas"].dim():  # a model whose tau is a scalar site
+            tau = tau[..., None]
+        return {"betas": tau * sites["lambdas"] * sites["unscaled_betas"]}
+
+    def flops_per_eval(self, num_chains):
+        """Algorithmic FLOPs of one evaluation (two GEMMs): 4 N D C."""
+        return 4.0 * self.N * self.D * num_chains
 
 
 class SoftmaxRegression(Potential):
@@ -545,6 +622,12 @@ softmax_regression = FusedModel(
 poisson_regression = FusedModel(
     "poisson_regression", lambda data, counts, offset=None: PoissonRegression(data, counts, offset),
     "coefs ~ Normal(0, 1) [D], obs ~ Poisson(exp(X @ coefs + offset)): model(data, counts, offset=None)")
+
+horseshoe_regression = FusedModel(
+    "horseshoe_regression",
+    lambda data, obs, likelihood="bernoulli", offset=None: HorseshoeRegression(data, obs, likelihood, offset),
+    "examples/horseshoe_regression.py:62-78 model_bernoulli_likelihood(X, Y), or with likelihood=\"poisson\" "
+    "Y ~ Poisson(exp(X @ betas + offset)): model(data, obs, likelihood=\"bernoulli\", offset=None)")
 
 eight_schools = FusedModel(
     "eight_schools", lambda J, sigma, y=None: EightSchools(J, sigma, y),
