@@ -537,6 +537,32 @@ size_t nmx_horseshoe_workspace_bytes(int likelihood, int64_t n_rows, int dim, in
 int nmx_horseshoe_pe_grad(int likelihood, const void* packed, int64_t n_rows, int dim, const nmx_eval_batch* ev,
                           void* workspace, void* stream);
 
+/* Negative-binomial (over-dispersed count) regression on the same kernel, the likelihood policy with a
+ * latent of its own (csrc/potential_logreg_wide.hip): coefs ~ N(0,1)^D, phi ~ Gamma(prior_a, prior_b)
+ * (shape, rate; Exponential(r) is Gamma(1, r)), obs ~ NegativeBinomial2(exp(X @ coefs + offset), phi).
+ * dim is the number of features D, 1 <= D <= 1024; the eval batch has D + 1 unconstrained rows: the
+ * coefficients (rows 0..D-1) and u = log phi (row D).  With eta = X b + offset, l = eta - u,
+ * sp(l) = max(l, 0) + log1p(exp(-|l|)), p = sigmoid(l), R(phi, y) = lgamma(phi + y) - lgamma(phi):
+ *   U     = sum_n [(phi + y_n) sp(l_n) - y_n l_n - R(phi, y_n) + lgamma(y_n + 1)]
+ *           + sum_d [b_d^2 / 2 + log(2 pi) / 2] - [a u - b phi] + lgamma(a) - a log b
+ *   dU/db = X^T res + b,  res_n = (phi + y_n) p_n - y_n
+ *   dU/du = sum_n [phi sp(l_n) - res_n - phi (digamma(phi + y_n) - digamma(phi))] - a + b phi
+ * Arguments and count rules as nmx_poisson_*; prior_a, prior_b finite and > 0.  nmx_negbin_pack
+ * synchronises the stream twice (the count check, which brings a copy of y to the host, and the upload
+ * of what the host makes of it): behind the tiles the packed image holds the distinct counts in
+ * ascending order with their multiplicities, K <= n_rows float64 pairs.  The R terms are summed over
+ * that table, per chain, by a kernel of their own in float64 and a fixed order (typical counts have a
+ * few hundred distinct values; K = n_rows is correct and merely slow).  The workspace holds three
+ * float64 rows per row split and two more.  Three launches; determinism as nmx_logreg_wide_*.  A huge
+ * eta overflows nothing; a chain whose u passes float32's exp range gets a non-finite U, and no other
+ * chain of the launch changes by a bit. */
+size_t nmx_negbin_packed_bytes(int64_t n_rows, int dim);
+int nmx_negbin_pack(const float* X, const float* y, const float* offset, int64_t n_rows, int dim, double prior_a,
+                    double prior_b, void* packed, void* stream);
+size_t nmx_negbin_workspace_bytes(int64_t n_rows, int dim, int num_chains);
+int nmx_negbin_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch* ev, void* workspace,
+                       void* stream);
+
 /* Softmax (multinomial logistic) regression: coefs ~ N(0,1)^(D x K),
  * obs ~ Categorical(logits = X @ coefs), coordinate of coefs[d][k] = d K + k (ravel order):
  *   U(W)  = sum_n [logsumexp_k l_nk - l_{n, y_n}] + sum_dk [W_dk^2 / 2 + log(2 pi) / 2],  l = X W

@@ -98,6 +98,40 @@
 // NB = ceil(D / HS_BLOCK): every order above is a function of D and S alone.  No atomics.  A chain whose
 // ut + ul[d] passes float32's exp range has beta = +-inf in its own B-operand column and in its own
 // float64 sums: U is not finite, and no other chain changes by a bit.
+//
+// lk_negbin is over-dispersed count regression, the first likelihood with a latent of its own:
+//
+//   coefs ~ N(0, 1)^D,  phi ~ Gamma(a, b),  obs ~ NegativeBinomial2(exp(X @ coefs + offset), phi)
+//
+// on D + 1 arena rows, row D being u = log phi (pr_normal; 1 <= D <= 1024).  With eta = X b + o,
+// l = eta - u, sp(l) = max(l, 0) + log1p(exp(-|l|)) (so log(phi + mu) = u + sp(l): nothing overflows in
+// eta), p = sigmoid(l) and R(phi, y) = lgamma(phi + y) - lgamma(phi):
+//
+//   U      = phi S1 + S2 - sum_n y_n l_n - sum_n R(phi, y_n) + sum_n lgamma(y_n + 1)
+//            + sum_d [b_d^2 / 2 + log(2 pi) / 2] - [a u - b phi] + lgamma(a) - a log b
+//   res_n  = (phi + y_n) p_n - y_n,   S1 = sum_n sp(l_n),  S2 = sum_n y_n sp(l_n),  S3 = sum_n res_n
+//   dU/db  = X^T res + b
+//   dU/du  = phi S1 - S3 - phi sum_n [digamma(phi + y_n) - digamma(phi)] - a + b phi
+//
+// The pack is Poisson's (side slot, X^T y, the constant, the count check).  The tile kernel loads u for
+// its lane's chain beside the gather (in the GEMM1 accumulator the chain is the lane), forms
+// phi = nb_phi(u) once, and runs the Bernoulli epilogue's arithmetic on l; slice 0 keeps S1, S2 and S3
+// as three float64 sums per lane, which leave through three pepart rows per split, added in the U
+// slabs' order.  A masked row has l = -inf: sp = 0, p = 0 and res = 0 exactly, no select.
+//
+// The eta-free part, sum_n R(phi, y_n) and its phi-derivative, is a sum over the DISTINCT counts: the
+// pack appends a table (y_k, m_k) of the distinct values in ascending order with their multiplicities
+// (float64 pairs, K <= N; built on the host from one copy of y), and k_negbin_rising sums it per chain
+// in float64 through the cancellation-free forms of NMX_OP_LRISING (nmx_program.h, restated in
+// float64: nb_lrising = R - y log phi and nb_lrising_da = dR/dphi - y / phi, never a difference of two
+// lgamma or digamma values).  The y log phi parts meet sum_n y_n l_n = <X^T y, b> + sum y o - u sum y:
+// u sum y cancels EXACTLY, so U takes -LR = -sum_k m_k nb_lrising(phi, y_k), and dU/du takes
+// -phi LD - sum y with LD = sum_k m_k nb_lrising_da(phi, y_k).  Eight chains x 32 table slices per
+// workgroup; slice s adds the entries s, s + 32, ... in table order and the 32 are added by a fixed
+// tree: a function of the table alone.  The plain finalize has two more rows for this policy: j = D is
+// dU/du and j = D + 1 is U, all float64 until the store.  A chain whose u passes float32's exp range
+// has phi = +inf in its own column and its own finalize lane: its U is not finite, and no other chain
+// changes by a bit.
 #include <math.h>
 #include <stdlib.h>
 
@@ -344,10 +378,42 @@ __device__ __forceinline__ void lw_epilogue_poisson(const nmx_f32x16& acc, const
   }
 }
 
+// Negative-binomial epilogue: `acc` is eta, `lu` the lane's chain's u = log phi.  The Bernoulli
+// epilogue's e, u, sigmoid and log1p on l = eta - lu; res = (phi + y) p - y formed here, per row, before
+// the bf16 split; slice 0 adds sp, y sp (an exact float64 product) and res to its three sums.  A masked
+// row has eta = -inf and y = 0: e = 0, p = 0, sp = 0 and res = 0 exactly.
+__device__ __forceinline__ float nb_phi(float lu) { return expf(lu); }
+template <bool ACC>
+__device__ __forceinline__ void lw_epilogue_negbin(const nmx_f32x16& acc, int k, const f32x4& yk, float lu, float phi,
+                                                   float (&res)[16], double& s1, double& s2, double& s3) {
+  // the registers 4 k .. 4 k + 3 and their counts yk
+#pragma unroll
+  for (int r = 4 * k; r < 4 * k + 4; ++r) {
+    const float l = acc[r] - lu, yv = yk[r & 3];
+    const float e = __builtin_amdgcn_exp2f(-fabsf(l) * LOG2E);
+    const float u = 1.0f + e;
+    const float s = __builtin_amdgcn_rcpf(u);
+    res[r] = (phi + yv) * (l >= 0.0f ? s : e * s) - yv;
+    if constexpr (ACC) {
+      const float dm = u - 1.0f;
+      const float lg = __builtin_amdgcn_logf(u) * LN2;
+      const float l1p = dm == 0.0f ? e : lg * (e * __builtin_amdgcn_rcpf(dm));
+      const float sp = fmaxf(l, 0.0f) + l1p;
+      s1 += (double)sp;
+      s2 = fma((double)yv, (double)sp, s2);
+      s3 += (double)res[r];
+    }
+  }
+}
+
 // The likelihood policies: the widths served, the bytes between the X^T y table and the tiles, what
-// the pack puts into the side slot, and the epilogue.
+// the pack puts into the side slot, and the epilogue; NPE float64 rows of pepart per split, whether
+// arena row D is a latent of the likelihood's own (lk_negbin: two more finalize rows, two workspace
+// rows of k_negbin_rising), and the bytes per row that follow the tiles.
 struct lk_bernoulli {
-  static constexpr int MIN_D = 65;
+  static constexpr int MIN_D = 65, NPE = 1;
+  static constexpr bool LATENT = false;
+  static constexpr size_t TAIL_PER_ROW = 0;
   static constexpr size_t HEAD_BYTES = 0;
   static constexpr int SIDE_QUADS = 8;      // 16-byte items of the side slot that hold data
   static constexpr bool HAS_OFFSET = false;  // entries 32..63 of the side slot are added to the logits
@@ -362,7 +428,9 @@ struct lk_bernoulli {
   }
 };
 struct lk_poisson {
-  static constexpr int MIN_D = 1;
+  static constexpr int MIN_D = 1, NPE = 1;
+  static constexpr bool LATENT = false;
+  static constexpr size_t TAIL_PER_ROW = 0;
   static constexpr size_t HEAD_BYTES = 256;  // float64 constant of U | the bad-count slot
   static constexpr int SIDE_QUADS = 16;
   static constexpr bool HAS_OFFSET = true;
@@ -377,6 +445,16 @@ struct lk_poisson {
                                                   double& pe) {
     lw_epilogue_poisson<ACC>(acc, y4, res, pe);
   }
+};
+// Poisson's pack and side slot; the kernel calls lw_epilogue_negbin itself (it has the chain's u).
+// Head, float64: [0] Poisson's constant, [1] the bad-count slot, then NB_A.. below; after the tiles
+// the table of distinct counts, n_rows pairs (y_k, m_k) of which the first head[NB_K] are set.
+enum { NB_A = 2, NB_B, NB_PRIOR, NB_K, NB_SUMY, NB_HEAD_END };  // a, b, lgamma(a) - a log b, K, sum_n y_n
+struct lk_negbin : lk_poisson {
+  static constexpr int NPE = 3;
+  static constexpr bool LATENT = true;
+  static constexpr size_t TAIL_PER_ROW = 2 * sizeof(double);
+  static constexpr const char* NAME = "negbin";
 };
 
 // Horseshoe scale and coefficient of one coordinate, s = exp(ut + ul) and beta = s z in float32: the
@@ -492,6 +570,13 @@ __global__ __launch_bounds__(64 * CT * DS) void k_logreg_wide(const char* __rest
 #pragma unroll
     for (int r = 0; r < 16; ++r) g[dt][r] = 0.0f;
   double pe = 0.0;
+  // lk_negbin: the chain's u = log phi (arena row D) and phi; pe, pe2 and pe3 are S1, S2 and S3
+  [[maybe_unused]] float lu = 0.0f, phi = 0.0f;
+  [[maybe_unused]] double pe2 = 0.0, pe3 = 0.0;
+  if constexpr (LK::LATENT) {
+    lu = ev.z[(size_t)D * ldc + cz];
+    phi = nb_phi(lu);
+  }
 
   char* const ring = lds + C::RING_OFF + sl * R * LW_CHUNK;      // the slice's R chunk slots
   char* const lab = lds + C::LAB_OFF + wu * 2 * LW_LABEL_BYTES;  // the wave's two label slots
@@ -621,14 +706,37 @@ __global__ __launch_bounds__(64 * CT * DS) void k_logreg_wide(const char* __rest
             for (int m = 0; m < 4; ++m) acc[4 * k + m] += y4[k][m];
           }
         }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) lw_lds_read(y4[k], la + 16 * k);
-        lw_lds_wait();
-#pragma unroll
-        for (int k = 0; k < 4; ++k) lw_pin(y4[k]);
         float res[16];
-        if (sl == 0) LK::template epilogue<true>(acc, y4, res, pe);
-        else LK::template epilogue<false>(acc, y4, res, pe);
+        if constexpr (LK::LATENT) {
+          // the counts come four rows at a time (three more LDS round trips per tile): with two float
+          // and two float64 values more than Poisson's live across the loop, sixteen counts beside the
+          // epilogue's temporaries would not fit the widest slices' registers
+          if (sl == 0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              lw_lds_read(y4[0], la + 16 * k);
+              lw_lds_wait();
+              lw_pin(y4[0]);
+              lw_epilogue_negbin<true>(acc, k, y4[0], lu, phi, res, pe, pe2, pe3);
+            }
+          } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              lw_lds_read(y4[0], la + 16 * k);
+              lw_lds_wait();
+              lw_pin(y4[0]);
+              lw_epilogue_negbin<false>(acc, k, y4[0], lu, phi, res, pe, pe2, pe3);
+            }
+          }
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) lw_lds_read(y4[k], la + 16 * k);
+          lw_lds_wait();
+#pragma unroll
+          for (int k = 0; k < 4; ++k) lw_pin(y4[k]);
+          if (sl == 0) LK::template epilogue<true>(acc, y4, res, pe);
+          else LK::template epilogue<false>(acc, y4, res, pe);
+        }
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
           float v[8];
@@ -672,7 +780,106 @@ __global__ __launch_bounds__(64 * CT * DS) void k_logreg_wide(const char* __rest
   if (sl == 0) {
     // the two lane halves hold the rows' two halves; lane + 32 is the same chain
     const double p = pe + __shfl_xor(pe, 32);
-    if (h == 0) pepart[(size_t)split * ldc + pos] = p;
+    if (h == 0) pepart[(size_t)split * LK::NPE * ldc + pos] = p;
+    if constexpr (LK::NPE == 3) {
+      const double p2 = pe2 + __shfl_xor(pe2, 32), p3 = pe3 + __shfl_xor(pe3, 32);
+      if (h == 0) {
+        pepart[((size_t)split * 3 + 1) * ldc + pos] = p2;
+        pepart[((size_t)split * 3 + 2) * ldc + pos] = p3;
+      }
+    }
+  }
+}
+
+// ---- lk_negbin's eta-free term.  The forms of NMX_OP_LRISING (nmx_program.h: the same branches, shift
+// and series, whose cuts are below 1e-11) in float64, for whole k >= 0:
+//   nb_lrising(a, k)    = lgamma(a + k) - lgamma(a) - k log(a)
+//   nb_lrising_da(a, k) = digamma(a + k) - digamma(a) - k / a
+// a = +inf or a = 0 (a chain whose u left float32's exp range) gives NaN: that chain's own U.
+__device__ __forceinline__ double nb_log1pmx(double t) {  // log1p(t) - t, t >= 0
+  if (!(t < 0.5)) return log1p(t) - t;
+  const double s = t / (2.0 + t), s2 = s * s;
+  double odd = 1.0 / 15 + s2 * (1.0 / 17);
+  odd = 1.0 / 9 + s2 * (1.0 / 11 + s2 * (1.0 / 13 + s2 * odd));
+  odd = 1.0 / 3 + s2 * (1.0 / 5 + s2 * (1.0 / 7 + s2 * odd));
+  return s * (2.0 * s2 * odd - t);
+}
+__device__ __forceinline__ double nb_stirling_s(double x) {  // lgamma's Stirling tail, x >= 8
+  const double r = 1.0 / x, r2 = r * r;
+  return (1.0 / 12 - (1.0 / 360 - (1.0 / 1260 - (1.0 / 1680) * r2) * r2) * r2) * r;
+}
+__device__ __forceinline__ double nb_stirling_ds(double x) {
+  const double r = 1.0 / x, r2 = r * r;
+  return -r2 * (1.0 / 12 - r2 * (1.0 / 120 - r2 * (1.0 / 252 - r2 * (1.0 / 240))));
+}
+constexpr int NB_SUM_MAX = 8;  // NMX_LRISING_SUM_MAX
+__device__ __forceinline__ void nb_lrising(double a, double k, double& val, double& da) {
+  if (!(a > 0.0)) {
+    val = da = NAN;
+    return;
+  }
+  if (k <= (double)NB_SUM_MAX) {
+    double s = 0.0, t = 0.0;
+    for (int j = 1; j < NB_SUM_MAX; ++j)
+      if ((double)j < k) {
+        s += log1p((double)j / a);
+        t += (double)j / (a * (a + (double)j));
+      }
+    val = s, da = -t;
+    return;
+  }
+  double x = a, shift = 0.0, dshift = 0.0, m = 0.0;
+  for (int j = 0; j < 8 && x < 8.0; ++j) {
+    shift += log1p(k / x);
+    dshift += k / (x * (x + k));
+    x += 1.0;
+    m += 1.0;
+  }
+  const double t = k / x, lm = nb_log1pmx(t);
+  val = x * lm + (k - 0.5) * log1p(t) + (nb_stirling_s(x + k) - nb_stirling_s(x)) + (k * log1p(m / a) - shift);
+  da = lm + 0.5 * k / (x * (x + k)) + (nb_stirling_ds(x + k) - nb_stirling_ds(x)) + (dshift - k * m / (a * x));
+}
+
+// rise[pos] = sum_k m_k nb_lrising(phi, y_k) and rise[ldc + pos] = sum_k m_k nb_lrising_da(phi, y_k) of
+// the chain at batch position pos, over the table's K = head[NB_K] pairs (y_k, m_k).  A workgroup is
+// RS_CHAINS positions x RS_SLICES table slices: slice s adds the entries s, s + RS_SLICES, ... in
+// table order, then the slices are added by a fixed tree.  The value depends on the table and the
+// chain's u alone.  K is a few hundred for typical counts; K = n_rows is correct and merely slow.
+constexpr int RS_THREADS = 256, RS_CHAINS = 8, RS_SLICES = RS_THREADS / RS_CHAINS;
+__global__ __launch_bounds__(RS_THREADS) void k_negbin_rising(const double* __restrict__ table,
+                                                              const double* __restrict__ head, int64_t n_rows, int D,
+                                                              nmx_eval_batch ev, double* __restrict__ rise) {
+  __shared__ double red[2][RS_SLICES][RS_CHAINS];
+  const int ci = threadIdx.x % RS_CHAINS, sl = threadIdx.x / RS_CHAINS;
+  const int pos = blockIdx.x * RS_CHAINS + ci;
+  const int ldc = ev.ldc;
+  const int c = pos < ldc ? nmx_eval_chain(ev, pos) : -1;
+  int64_t K = (int64_t)head[NB_K];
+  NMX_DCHECK(K >= 1 && K <= n_rows);
+  if (K > n_rows) K = n_rows;  // the table's capacity
+  double r = 0.0, d = 0.0;
+  if (c >= 0) {
+    const double phi = (double)nb_phi(ev.z[(size_t)D * ldc + c]);
+    for (int64_t k = sl; k < K; k += RS_SLICES) {
+      double v, dv;
+      nb_lrising(phi, table[2 * k], v, dv);
+      r += table[2 * k + 1] * v;
+      d += table[2 * k + 1] * dv;
+    }
+  }
+  red[0][sl][ci] = r;
+  red[1][sl][ci] = d;
+  __syncthreads();
+  for (int k = RS_SLICES / 2; k > 0; k >>= 1) {
+    if (sl < k) {
+      red[0][sl][ci] += red[0][sl + k][ci];
+      red[1][sl][ci] += red[1][sl + k][ci];
+    }
+    __syncthreads();
+  }
+  if (sl == 0 && c >= 0) {
+    rise[pos] = red[0][0][ci];
+    rise[(size_t)ldc + pos] = red[1][0][ci];
   }
 }
 
@@ -680,13 +887,16 @@ __global__ __launch_bounds__(64 * CT * DS) void k_logreg_wide(const char* __rest
 // [w S / 4, (w + 1) S / 4) in order -- and, on the U row, its quarter of the coordinates'
 // z^2 / 2 - xty z in float64 -- then the four wave sums are added in wave order.  A policy with a
 // head adds its float64 constant (xty[LW_MAX_D]) once per chain, last.
+// lk_negbin has the rows j = D (dU/du) and j = D + 1 (U): both sum the three pepart rows of every
+// split the same way (the coordinates' part joins S2 on the U row), then combine them in float64 with
+// phi = nb_phi(u), k_negbin_rising's two rows (behind the pepart slabs), the head and the Gamma prior.
 constexpr int FIN_WAVES = 4;
 template <class LK>
 __global__ __launch_bounds__(64 * FIN_WAVES) void k_logreg_wide_finalize(const float* __restrict__ gpart,
                                                                          const double* __restrict__ pepart, int S,
                                                                          int D, nmx_eval_batch ev,
                                                                          const double* __restrict__ xty) {
-  __shared__ double part[FIN_WAVES][64];
+  __shared__ double part[LK::NPE][FIN_WAVES][64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int pos = blockIdx.x * 64 + lane;
   const int j = blockIdx.y;
@@ -700,29 +910,61 @@ __global__ __launch_bounds__(64 * FIN_WAVES) void k_logreg_wide_finalize(const f
       for (int sp = sp0; sp < sp1; ++sp) f += gpart[((size_t)sp * D + j) * ldc + pos];
       s = f;
     } else {
-      for (int sp = sp0; sp < sp1; ++sp) s += pepart[(size_t)sp * ldc + pos];
-      const int j0 = w * D / FIN_WAVES, j1 = (w + 1) * D / FIN_WAVES;
-      double q = 0.0;
-      for (int jj = j0; jj < j1; ++jj) {
-        const double z = ev.z[(size_t)jj * ldc + c];
-        q += 0.5 * z * z - xty[jj] * z;
+      [[maybe_unused]] double s2 = 0.0, s3 = 0.0;
+      for (int sp = sp0; sp < sp1; ++sp) {
+        s += pepart[(size_t)sp * LK::NPE * ldc + pos];
+        if constexpr (LK::NPE == 3) {
+          s2 += pepart[((size_t)sp * 3 + 1) * ldc + pos];
+          s3 += pepart[((size_t)sp * 3 + 2) * ldc + pos];
+        }
       }
-      s += q;
+      double q = 0.0;
+      if (!LK::LATENT || j == D + 1) {
+        const int j0 = w * D / FIN_WAVES, j1 = (w + 1) * D / FIN_WAVES;
+        for (int jj = j0; jj < j1; ++jj) {
+          const double z = ev.z[(size_t)jj * ldc + c];
+          q += 0.5 * z * z - xty[jj] * z;
+        }
+      }
+      if constexpr (LK::NPE == 3) {
+        part[1][w][lane] = s2 + q;
+        part[2][w][lane] = s3;
+      } else {
+        s += q;
+      }
     }
-    part[w][lane] = s;
+    part[0][w][lane] = s;
   }
   __syncthreads();
   if (w != 0 || c < 0) return;
   if (j < D) {
     float s = 0.0f;
 #pragma unroll
-    for (int i = 0; i < FIN_WAVES; ++i) s += (float)part[i][lane];
+    for (int i = 0; i < FIN_WAVES; ++i) s += (float)part[0][i][lane];
     const size_t idx = (size_t)j * ldc + c;
     ev.grad[idx] = ev.z[idx] + s;
+  } else if constexpr (LK::LATENT) {
+    double S1 = 0.0, S2 = 0.0, S3 = 0.0;
+#pragma unroll
+    for (int i = 0; i < FIN_WAVES; ++i) {
+      S1 += part[0][i][lane];
+      S2 += part[1][i][lane];
+      S3 += part[2][i][lane];
+    }
+    const double* head = xty + LW_MAX_D;
+    const double* rise = pepart + (size_t)S * 3 * ldc;
+    const size_t iu = (size_t)D * ldc + c;
+    const float uf = ev.z[iu];
+    const double u = uf, phi = nb_phi(uf), a = head[NB_A], b = head[NB_B];
+    if (j == D)
+      ev.grad[iu] = (float)(phi * S1 - S3 - phi * rise[(size_t)ldc + pos] - head[NB_SUMY] - a + b * phi);
+    else
+      ev.pe[c] = (float)(phi * S1 + S2 + 0.9189385332046727 * D + head[0] - rise[pos] - (a * u - b * phi) +
+                         head[NB_PRIOR]);
   } else {
     double s = 0.0;
 #pragma unroll
-    for (int i = 0; i < FIN_WAVES; ++i) s += part[i][lane];
+    for (int i = 0; i < FIN_WAVES; ++i) s += part[0][i][lane];
     s += 0.9189385332046727 * D;
     if constexpr (LK::HEAD_BYTES > 0) s += xty[LW_MAX_D];
     ev.pe[c] = (float)s;
@@ -884,7 +1126,8 @@ int lw_launch_dts(int DTS, const lw_args& a) {
 template <class LK, class PR = pr_normal>
 size_t lw_packed_bytes(int64_t n_rows, int dim) {
   if (!lw_shape_ok(n_rows, dim, lw_min_d<LK, PR>())) return 0;
-  return LW_XTY_BYTES + LK::HEAD_BYTES + (size_t)lw_ntiles(n_rows) * lw_tile_bytes(dim);
+  return LW_XTY_BYTES + LK::HEAD_BYTES + (size_t)lw_ntiles(n_rows) * lw_tile_bytes(dim) +
+         (size_t)n_rows * LK::TAIL_PER_ROW;
 }
 
 template <class LK>
@@ -899,14 +1142,16 @@ int lw_pack(const float* X, const float* y, const float* off, int64_t n_rows, in
   return nmx_check_launch("k_logreg_wide_pack");
 }
 
-// workspace: the gradient slabs | the U slabs | (horseshoe) the blocks' U rows | their beta G rows
+// workspace: the gradient slabs | the U slabs, LK::NPE rows per split | (horseshoe) the blocks' U rows |
+// their beta G rows | (lk_negbin) k_negbin_rising's two rows
 template <class LK, class PR = pr_normal>
 size_t lw_workspace_bytes(int64_t n_rows, int dim, int num_chains) {
   if (!lw_shape_ok(n_rows, dim, lw_min_d<LK, PR>()) || num_chains <= 0) return 0;
   const size_t ldc = (size_t)(num_chains + 63) / 64 * 64;
   const size_t S = lw_num_splits(n_rows, dim);
   const size_t g = S * dim * ldc * sizeof(float);
-  const size_t p = (S + (PR::HORSESHOE ? 2 * hs_num_blocks(dim) : 0)) * ldc * sizeof(double);
+  const size_t p =
+      (S * LK::NPE + (PR::HORSESHOE ? 2 * hs_num_blocks(dim) : 0) + (LK::LATENT ? 2 : 0)) * ldc * sizeof(double);
   return (g + 255) / 256 * 256 + p;
 }
 
@@ -935,6 +1180,13 @@ int lw_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch
   else st = lw_launch_dts<LK, PR, 1, 8, 2>(c.DTS, a);
   if (st) return st;
   if (int e = nmx_check_launch("k_logreg_wide")) return e;
+  if constexpr (LK::LATENT) {
+    const double* head = (const double*)((const char*)packed + LW_XTY_BYTES);
+    const double* table = (const double*)(a.Xq + (size_t)a.nt * lw_tile_bytes(dim));
+    hipLaunchKernelGGL(k_negbin_rising, dim3((nb + RS_CHAINS - 1) / RS_CHAINS), dim3(RS_THREADS), 0, s, table, head,
+                       n_rows, dim, *ev, pepart + (size_t)S * LK::NPE * ev->ldc);
+    if (int e = nmx_check_launch("k_negbin_rising")) return e;
+  }
   if constexpr (PR::HORSESHOE) {
     const int NB = hs_num_blocks(dim);
     double* upart = pepart + (size_t)S * ev->ldc;
@@ -946,8 +1198,8 @@ int lw_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch
                        dim, NB, *ev, (const double*)packed);
     return nmx_check_launch("k_horseshoe_tau");
   } else {
-    hipLaunchKernelGGL(k_logreg_wide_finalize<LK>, dim3((nb + 63) / 64, dim + 1), dim3(64 * FIN_WAVES), 0, s, gpart,
-                       pepart, S, dim, *ev, (const double*)packed);
+    hipLaunchKernelGGL(k_logreg_wide_finalize<LK>, dim3((nb + 63) / 64, dim + 1 + LK::LATENT), dim3(64 * FIN_WAVES), 0,
+                       s, gpart, pepart, S, dim, *ev, (const double*)packed);
     return nmx_check_launch("k_logreg_wide_finalize");
   }
 }
@@ -966,6 +1218,62 @@ int lw_poisson_pack(const char* name, const float* X, const float* y, const floa
     return nmx_fail(NMX_ERR_HIP, "%s_pack: reading the count check back failed", name);
   if (first != ~0ull)
     return nmx_fail(NMX_ERR_INVALID, "%s_pack: the count of row %llu is not a whole number in [0, 2^24)", name, first);
+  return lw_pack<lk_poisson>(X, y, offset, n_rows, dim, packed, s);
+}
+
+// Negative-binomial pack: Poisson's count check, constant, X^T y and tiles, then the head's scalars and
+// the table of distinct counts, built on the host from the copy of y that comes back with the check
+// (sorted, run lengths as float64; sum y is exact, whole numbers below 2^53).  Two synchronisations:
+// the check with the copy of y, and the upload from the pinned staging buffer before it is freed.
+int lw_negbin_pack(const float* X, const float* y, const float* offset, int64_t n_rows, int dim, double prior_a,
+                   double prior_b, void* packed, hipStream_t s) {
+  double* head = (double*)((char*)packed + LW_XTY_BYTES);
+  unsigned long long* bad = (unsigned long long*)(head + 1);
+  hipLaunchKernelGGL(k_poisson_bad_reset, dim3(1), dim3(1), 0, s, bad);
+  hipLaunchKernelGGL(k_poisson_const, dim3(1), dim3(CS_THREADS), 0, s, y, offset, n_rows, head, bad);
+  if (int st = nmx_check_launch("k_poisson_const")) return st;
+  // pinned staging: the table's n_rows pairs | NB_HEAD_END scalars | the copy of y
+  const size_t tab_bytes = (size_t)n_rows * lk_negbin::TAIL_PER_ROW;
+  char* stage = nullptr;
+  if (hipHostMalloc((void**)&stage, tab_bytes + NB_HEAD_END * sizeof(double) + (size_t)n_rows * sizeof(float)) !=
+      hipSuccess)
+    return nmx_fail(NMX_ERR_HIP, "negbin_pack: no pinned staging memory for %lld counts", (long long)n_rows);
+  double* tab = (double*)stage;
+  double* hs = tab + 2 * n_rows;
+  float* hy = (float*)(hs + NB_HEAD_END);
+  unsigned long long* first = (unsigned long long*)hs;  // read before the scalars are written
+  int st = NMX_OK;
+  if (hipMemcpyAsync(hy, y, (size_t)n_rows * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(first, bad, sizeof(*first), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    st = nmx_fail(NMX_ERR_HIP, "negbin_pack: reading the count check back failed");
+  else if (*first != ~0ull)
+    st = nmx_fail(NMX_ERR_INVALID, "negbin_pack: the count of row %llu is not a whole number in [0, 2^24)", *first);
+  if (st == NMX_OK) {
+    std::sort(hy, hy + n_rows);
+    int64_t K = 0;
+    double sumy = 0.0;
+    for (int64_t i = 0; i < n_rows; ++i) {
+      if (i == 0 || hy[i] != hy[i - 1]) {
+        tab[2 * K] = hy[i];
+        tab[2 * K + 1] = 0.0;
+        ++K;
+      }
+      tab[2 * K - 1] += 1.0;
+      sumy += hy[i];
+    }
+    hs[NB_A] = prior_a, hs[NB_B] = prior_b, hs[NB_PRIOR] = lgamma(prior_a) - prior_a * log(prior_b);
+    hs[NB_K] = (double)K, hs[NB_SUMY] = sumy;
+    char* tiles = (char*)packed + LW_XTY_BYTES + lk_negbin::HEAD_BYTES;
+    if (hipMemcpyAsync(head + NB_A, hs + NB_A, (NB_HEAD_END - NB_A) * sizeof(double), hipMemcpyHostToDevice, s) !=
+            hipSuccess ||
+        hipMemcpyAsync(tiles + (size_t)lw_ntiles(n_rows) * lw_tile_bytes(dim), tab, (size_t)K * 2 * sizeof(double),
+                       hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+      st = nmx_fail(NMX_ERR_HIP, "negbin_pack: writing the table of counts failed");
+  }
+  (void)hipHostFree(stage);
+  if (st) return st;
   return lw_pack<lk_poisson>(X, y, offset, n_rows, dim, packed, s);
 }
 
@@ -1008,6 +1316,28 @@ extern "C" size_t nmx_poisson_workspace_bytes(int64_t n_rows, int dim, int num_c
 extern "C" int nmx_poisson_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch* ev,
                                    void* workspace, void* stream) {
   return lw_pe_grad<lk_poisson>(packed, n_rows, dim, ev, workspace, stream);
+}
+
+// Negative-binomial regression: `dim` is the number of features D, the arena has D + 1 rows.
+extern "C" size_t nmx_negbin_packed_bytes(int64_t n_rows, int dim) { return lw_packed_bytes<lk_negbin>(n_rows, dim); }
+
+extern "C" int nmx_negbin_pack(const float* X, const float* y, const float* offset, int64_t n_rows, int dim,
+                               double prior_a, double prior_b, void* packed, void* stream) {
+  if (int st = lw_check_shape("negbin", "pack", n_rows, dim, lk_negbin::MIN_D)) return st;
+  if (!X || !y || !packed) return nmx_fail(NMX_ERR_INVALID, "negbin_pack: NULL pointer");
+  if (!(prior_a > 0.0 && prior_a < INFINITY && prior_b > 0.0 && prior_b < INFINITY))
+    return nmx_fail(NMX_ERR_INVALID, "negbin_pack: the Gamma prior needs finite a, b > 0 (got %g, %g)", prior_a,
+                    prior_b);
+  return lw_negbin_pack(X, y, offset, n_rows, dim, prior_a, prior_b, packed, (hipStream_t)stream);
+}
+
+extern "C" size_t nmx_negbin_workspace_bytes(int64_t n_rows, int dim, int num_chains) {
+  return lw_workspace_bytes<lk_negbin>(n_rows, dim, num_chains);
+}
+
+extern "C" int nmx_negbin_pe_grad(const void* packed, int64_t n_rows, int dim, const nmx_eval_batch* ev,
+                                  void* workspace, void* stream) {
+  return lw_pe_grad<lk_negbin>(packed, n_rows, dim, ev, workspace, stream);
 }
 
 // Horseshoe-prior regression: `likelihood` is 0 (Bernoulli logits) or 1 (Poisson, log link); `dim`

@@ -9,7 +9,7 @@ differentiates it with JAX.  Here the trace records each site's distribution, pa
 observed data; a matcher per supported structure checks the priors' constants and the
 likelihood's expression and returns the bound fused potential, with the model's own site
 names.  Supported structures: the reference's examples on the hot path (covtype logistic
-regression, its multi-class form, softmax regression, Poisson regression, and horseshoe regression; eight schools,
+regression, its multi-class form, softmax regression, Poisson and negative-binomial regression, and horseshoe regression; eight schools,
 funnel and its LocScaleReparam(0) form, stochastic volatility, the BNN) and the test targets (diagonal normal, multivariate normal).  For anything else
 potential_from_model raises NotImplementedError naming the traced sites; NUTS / HMC then hand
 the model to the program compiler (numpyro_amd/program.py compile_model), which lowers the
@@ -204,6 +204,55 @@ def _match_poisson(trace):
         return None
     w, o, X, offset = hit
     return _renamed(P.PoissonRegression(X, o.obs, offset), {"coefs": w.name})
+
+
+def _scalar(x):
+    """The value of a constant whose elements are all equal, or None."""
+    if not _const(x):
+        return None
+    a = _host(x).astype(np.float64).reshape(-1)
+    return float(a[0]) if a.size and np.all(a == a[0]) else None
+
+
+def _match_negbin(trace):
+    """coefs ~ Normal(0, 1)^D, phi ~ Gamma(a, b) or Exponential(r) of shape () or (1,) with constant
+    parameters, obs ~ NegativeBinomial2(mean=exp(X @ coefs [+ offset]), concentration=phi).  Nothing else:
+    no other prior, parametrisation (GammaPoisson, NegativeBinomial by probs), latent or term, a
+    concentration that is the site itself, a constant [N] offset, D <= 1024, whole counts."""
+    lat, obs = _split(trace)
+    if len(lat) != 2 or len(obs) != 1 or trace.reparam:
+        return None
+    w = [s for s in lat if _std_normal(s) and len(s.shape) == 1]
+    phi = [s for s in lat if type(_base(s.fn)) in (dist.Gamma, dist.Exponential) and s.shape in ((), (1,))]
+    if len(w) != 1 or len(phi) != 1:
+        return None
+    w, phi, o = w[0], phi[0], obs[0]
+    b = _base(phi.fn)
+    prior = (_scalar(b.concentration), _scalar(b.rate)) if isinstance(b, dist.Gamma) else (1.0, _scalar(b.rate))
+    if None in prior or not all(0 < v < float("inf") for v in prior):
+        return None
+    if type(_base(o.fn)) is not dist.NegativeBinomial2 or not _latent(_base(o.fn).concentration, phi.name):
+        return None
+    mean = _base(o.fn).mean
+    if not (isinstance(mean, Sym) and mean.op == "exp"):
+        return None
+    eta, offset = mean.args[0], None
+    if isinstance(eta, Sym) and eta.op == "add":
+        a, c = eta.args
+        eta, offset = (a, c) if isinstance(a, Sym) else (c, a)
+    if not (isinstance(eta, Sym) and eta.op == "matmul" and _const(eta.args[0]) and _latent(eta.args[1], w.name)):
+        return None
+    X = eta.args[0]
+    N, D = (tuple(shape_of(X)) + (0, 0))[:2]
+    if len(shape_of(X)) != 2 or D != w.shape[0] or not 1 <= D <= P.NegativeBinomialRegression.MAX_FEATURES:
+        return None
+    if offset is not None and not (_const(offset) and tuple(shape_of(offset)) == (N,)):
+        return None
+    if tuple(shape_of(o.obs)) != (N,) or not P.poisson_counts_ok(o.obs):
+        return None
+    pot = P.NegativeBinomialRegression(X, o.obs, offset, prior)
+    pot.sites[1] = ("phi", phi.shape, P.POSITIVE)
+    return _renamed(pot, {"coefs": w.name, "phi": phi.name})
 
 
 def _product_latents(x):
@@ -445,7 +494,7 @@ def _match_normal(trace):
     return None
 
 
-MATCHERS = (_match_logistic, _match_poisson, _match_horseshoe, _match_softmax, _match_eight_schools, _match_funnel, _match_sv, _match_bnn,
+MATCHERS = (_match_logistic, _match_poisson, _match_negbin, _match_horseshoe, _match_softmax, _match_eight_schools, _match_funnel, _match_sv, _match_bnn,
             _match_normal)
 
 
@@ -460,7 +509,7 @@ def potential_from_model(model, args=(), kwargs=None):
             return _with_traced_deterministics(pot, trace)
     raise NotImplementedError(
         "no fused kernel for this model structure (sites: " + ", ".join(map(repr, trace.sites.values())) +
-        "); supported: the reference's covtype logistic regression, softmax regression, Poisson regression, horseshoe regression (Bernoulli / Poisson), eight schools, funnel (+ LocScaleReparam), "
+        "); supported: the reference's covtype logistic regression, softmax regression, Poisson and negative-binomial regression, horseshoe regression (Bernoulli / Poisson), eight schools, funnel (+ LocScaleReparam), "
         "stochastic volatility and BNN examples, and diagonal / multivariate normal targets")
 
 

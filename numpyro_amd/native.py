@@ -252,6 +252,10 @@ SIGNATURES: dict[str, tuple] = {
     "nmx_horseshoe_pack": (c_int, [c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     "nmx_horseshoe_workspace_bytes": (c_size, [c_int, c_i64, c_int, c_int]),
     "nmx_horseshoe_pe_grad": (c_int, [c_int, c_vp, c_i64, c_int, _evp, c_vp, c_vp]),
+    "nmx_negbin_packed_bytes": (c_size, [c_i64, c_int]),
+    "nmx_negbin_pack": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, ctypes.c_double, ctypes.c_double, c_vp, c_vp]),
+    "nmx_negbin_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
+    "nmx_negbin_pe_grad": (c_int, [c_vp, c_i64, c_int, _evp, c_vp, c_vp]),
     "nmx_softmax_packed_bytes": (c_size, [c_i64, c_int, c_int]),
     "nmx_softmax_pack": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp]),
     "nmx_softmax_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int]),

@@ -307,6 +307,70 @@ class PoissonRegression(Potential):
         return 4.0 * self.N * self.dim * num_chains
 
 
+class NegativeBinomialRegression(Potential):
+    """Over-dispersed count regression: coefs ~ N(0, 1)^D, phi ~ Gamma(a, b) with ``prior=(a, b)`` (shape,
+    rate; Exponential(r) is (1, r)), obs ~ NegativeBinomial2(exp(X @ coefs + offset), phi).  1 to 1024
+    features on the D-blocked kernel of csrc/potential_logreg_wide.hip with the negative-binomial
+    likelihood policy (the ``nmx_negbin_*`` entry points); D + 1 coordinates, the last is log phi.
+    The lgamma terms are summed over the distinct counts: a few hundred for typical data; counts that
+    are all different stay correct and merely cost one lgamma-class evaluation per row and chain."""
+
+    MAX_FEATURES = 1024
+
+    def __init__(self, data, counts, offset=None, prior=(1.0, 1.0)):
+        self.X_in, self.y_in, self.o_in = data, counts, offset
+        shape, yshape = tuple(data.shape), tuple(getattr(counts, "shape", None) or np.shape(counts))
+        if len(shape) != 2 or yshape != shape[:1]:
+            raise ValueError(f"negative-binomial regression needs data [N, D] and counts [N] (got {shape}, {yshape})")
+        if offset is not None and tuple(getattr(offset, "shape", None) or np.shape(offset)) != yshape:
+            raise ValueError(f"negative-binomial regression needs an offset of shape {list(yshape)}")
+        self.N, self.D = int(shape[0]), int(shape[1])
+        if not 1 <= self.D <= self.MAX_FEATURES:
+            raise ValueError(f"the fused negative-binomial-regression kernel supports 1 to {self.MAX_FEATURES} "
+                             f"features (got {self.D})")
+        if not poisson_counts_ok(counts):
+            raise ValueError("negative-binomial regression needs counts that are whole numbers in [0, 2^24)")
+        try:
+            a, b = (float(v) for v in prior)
+        except (TypeError, ValueError):
+            a = b = float("nan")
+        if not (0 < a < float("inf") and 0 < b < float("inf")):
+            raise ValueError(f"negative-binomial regression needs a Gamma prior (a, b) with finite a, b > 0 (got {prior!r})")
+        self.prior = (a, b)
+        self.dim = self.D + 1
+        self.sites = [("coefs", (self.D,), REAL), ("phi", (), POSITIVE)]
+        self.packed = None
+
+    slots = 4  # workspaces, as LogisticRegression
+
+    def _bind(self, C, ldc, device):
+        if self.packed is None or self.packed.device != device:
+            X, y = _dev(self.X_in, device), _dev(self.y_in, device)
+            o = None if self.o_in is None else _dev(self.o_in, device)
+            nb = lib().nmx_negbin_packed_bytes(self.N, self.D)
+            self.packed = torch.empty(nb // 4, dtype=torch.float32, device=device)
+            with torch.cuda.device(device):
+                check(lib().nmx_negbin_pack(ptr(X), ptr(y), ptr(o), self.N, self.D, *self.prior, ptr(self.packed),
+                                            native.stream_ptr()), "nmx_negbin_pack")
+            del X, y, o
+        wb = lib().nmx_negbin_workspace_bytes(self.N, self.D, ldc)  # the slabs' rows are ldc wide
+        self.workspace = torch.empty(wb, dtype=torch.uint8, device=device)
+        self._more_ws = []  # slots 1.. (allocated on first use)
+
+    def evaluate(self, ev, stream, slot=0):
+        ws = self.workspace
+        if slot:
+            while len(self._more_ws) < slot:
+                self._more_ws.append(torch.empty_like(self.workspace))
+            ws = self._more_ws[slot - 1]
+        check(lib().nmx_negbin_pe_grad(ptr(self.packed), self.N, self.D, ctypes.byref(ev), ptr(ws), stream),
+              "nmx_negbin_pe_grad")
+
+    def flops_per_eval(self, num_chains):
+        """Algorithmic FLOPs of one evaluation (two GEMMs): 4 N D C."""
+        return 4.0 * self.N * self.D * num_chains
+
+
 class HorseshoeRegression(Potential):
     """examples/horseshoe_regression.py:62-78, sparse regression with a horseshoe prior:
     lambdas ~ HalfCauchy(1)^D, tau ~ HalfCauchy(1) [1], unscaled_betas ~ N(0, 1)^D,
@@ -622,6 +686,12 @@ softmax_regression = FusedModel(
 poisson_regression = FusedModel(
     "poisson_regression", lambda data, counts, offset=None: PoissonRegression(data, counts, offset),
     "coefs ~ Normal(0, 1) [D], obs ~ Poisson(exp(X @ coefs + offset)): model(data, counts, offset=None)")
+
+negative_binomial_regression = FusedModel(
+    "negative_binomial_regression",
+    lambda data, counts, offset=None, prior=(1.0, 1.0): NegativeBinomialRegression(data, counts, offset, prior),
+    "coefs ~ Normal(0, 1) [D], phi ~ Gamma(a, b), obs ~ NegativeBinomial2(exp(X @ coefs + offset), phi): "
+    "model(data, counts, offset=None, prior=(a, b))")
 
 horseshoe_regression = FusedModel(
     "horseshoe_regression",
